@@ -13,13 +13,18 @@ on the same 512^3 global grid (C3 "512^3 DoFs, 8 x MI355X"), z-slabs of the
 reference's formula (system.h:720-757); --weak gives every rank a 512-plane
 slab of a 512 x 512 x 512N grid instead.
 
-At N = 1 the line also carries the other two per-stage operations of the RK
-loop, timed the same way (HIP events on the operator's stream): the exact
-mass inverse (roofline.mass_solve) and one device-resident RK4 stage
-(compute_rhs + mass solve + fused stage updates + device boundary data,
-rk4_stage_ms).
+A plain run sets up, settles, warms up, times the K steps and prints the
+line.  With --full, at N = 1, the line also carries the other two per-stage
+operations of the RK loop, timed the same way (HIP events on the operator's
+stream): the exact mass inverse (roofline.mass_solve) and one device-resident
+RK4 stage (compute_rhs + mass solve + fused stage updates + device boundary
+data, rk4_stage_ms); the per-rank legs of C3 and C4 (c3_per_rank_8, c4_wave);
+the HBM traffic of the stencil from PMC counters (roofline.traffic) and the
+CPU baselines (cpu_baseline).  Without --full these entries are null.
+--dump-outputs DIR writes the vector the last timed step computed to
+DIR/compute_rhs.npy (above 32 MiB a fixed, seeded sample of its entries).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment
@@ -66,8 +71,38 @@ def parse():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--metric-only", action="store_true",
                     help="time only the metric's compute_rhs (no mass / RK-stage / PMC / CPU legs): for per-config "
-                         "rocprof kernel statistics")
+                         "rocprof kernel statistics; the default without --full")
+    ap.add_argument("--full", action="store_true",
+                    help="after the metric also run the other legs of the line (N = 1): mass solve, RK4 stage, the "
+                         "C3 / C4 per-rank legs, HBM PMC traffic, CPU baselines; without it they are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: all files (every rank's) together
+
+
+def dump_outputs(path, dst, rank, world):
+    """--dump-outputs: the vector the last timed compute_rhs wrote (this
+    rank's owned DoFs) as DIR/compute_rhs.npy (compute_rhs_rank<r>.npy at
+    N > 1), float64.  Above the size limit a fixed sample of it: the entries
+    at sorted indices drawn by a generator seeded with a constant, the same
+    from run to run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = dst.numel()
+    limit = DUMP_MAX_BYTES // 8 // world
+    if n > limit:
+        import torch
+
+        idx = np.sort(np.random.default_rng(20251014).integers(0, n, size=limit))
+        out = dst[torch.from_numpy(idx).to(dst.device)].cpu().numpy()
+    else:
+        out = dst.cpu().numpy()
+    name = "compute_rhs.npy" if world == 1 else "compute_rhs_rank%d.npy" % rank
+    np.save(os.path.join(path, name), np.ascontiguousarray(out, dtype=np.float64))
 
 
 def _band_csr(O, mesh, d, which):
@@ -696,6 +731,8 @@ def main():
     total_dofs = lay["n_dofs_global"]
     ms_per_step = elapsed / args.steps * 1e3
     value = total_dofs * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dst, rank, world)
 
     if rank != 0:
         if dist is not None:
@@ -704,7 +741,8 @@ def main():
 
     achieved = BYTES_PER_DOF * lay["n_owned"] / (kern_ms * 1e-3) / 1e9
     mass = stage_ms = None
-    if world == 1 and not args.metric_only:
+    legs = world == 1 and args.full and not args.metric_only  # everything below the metric
+    if legs:
         # the exact mass inverse (gdm_mass_solve; HIP events on the op stream) and one device-resident RK4
         # stage of the advection problem (AdvectionProblem.step / 4)
         op.time_op(2, dst, src[:lay["n_owned"]], None, 2)  # warm-up (first launches of the line-solve kernels)
@@ -729,14 +767,14 @@ def main():
             stage_ms = e0.elapsed_time(e1) / 12.0
             del prob
     c4 = c3r = None
-    if world == 1 and not args.metric_only:
+    if legs:
         c3r = c3_rank_slab()
         c4 = c4_wave_stage()
     traffic = None
-    if world == 1 and str(args.pmc) == "1" and not args.metric_only:
+    if legs and str(args.pmc) == "1":
         traffic = pmc_traffic(args)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.metric_only:
+    if legs and not args.no_cpu_baseline:
         try:
             # every CPU this process may run on: the affinity mask (nproc), bounded by the cgroup's CPU quota
             th, src = (args.cpu_threads, "--cpu-threads") if args.cpu_threads else cpu_threads()

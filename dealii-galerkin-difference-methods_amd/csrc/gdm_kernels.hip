@@ -1692,6 +1692,7 @@ __device__ __forceinline__ double face_step2_value(const double *__restrict__ T,
   return v;
 }
 
+#ifndef GDM_STENCIL_PART
 // dst node (t, i1) += scale sum_m w1[i1][m] T[q + m][t]: one face (face by face, in face order)
 __global__ void __launch_bounds__(256) face_step2_kernel(const double *__restrict__ T, int n0, int i1_begin,
                                                           int i1_end, const int *__restrict__ qs1,
@@ -1706,6 +1707,7 @@ __global__ void __launch_bounds__(256) face_step2_kernel(const double *__restric
   double *d = dst + base + (int64_t)t * stride0 + (int64_t)(i1 - i1_begin) * stride1;
   *d = *d + v;
 }
+#endif  // !GDM_STENCIL_PART
 
 // step-2 data of one face for face_step2_add_kernel
 struct Step2Face {
@@ -1813,6 +1815,7 @@ __global__ void __launch_bounds__(64) face_step2_add_kernel(const Step2AddSet se
   }
 }
 
+#ifndef GDM_STENCIL_PART
 // ---------------------------------------------------------------------------
 // BLAS-1
 // ---------------------------------------------------------------------------
@@ -1865,6 +1868,7 @@ __global__ void __launch_bounds__(256) zero_kernel(int64_t n, double *__restrict
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     y[i] = 0.0;
 }
+#endif  // !GDM_STENCIL_PART
 
 // ---------------------------------------------------------------------------
 // host-side launchers (called from gdm_capi.cpp)
@@ -1974,8 +1978,45 @@ static hipError_t launch8_p(int bk, const StencilArgs &a, const TailReq &tail, h
   }
 }
 
+// The stencil kernels of one degree take minutes to compile, so the build
+// compiles this file once per degree, side by side: a unit built with
+// -DGDM_STENCIL_PART=<p> holds only launch8_part<p> / launch7_part<p> (and the
+// kernels they instantiate), the main unit, built with -DGDM_STENCIL_SPLIT,
+// everything else and calls them.  With neither macro one unit holds it all.
+#define GDM_L8_1 launch8_p<1, 4, 8, 8, 3>
+#define GDM_L8_3 launch8_p<3, 4, 8, 8, 3>
+#define GDM_L8_5 launch8_p<5, GDM_R5, GDM_NC5, GDM_NP5, GDM_PF5>
+#define GDM_L8_7 launch8_p<7, GDM_R7, GDM_NC7, GDM_NP7, GDM_PF7>
+#define GDM_L8_9 launch8_p<9, 2, 8, 8, 3>
+#define GDM_L7_1 launch7_p<1, 4, 8, 8>
+#define GDM_L7_3 launch7_p<3, 4, 8, 8>
+#define GDM_L7_5 launch7_p<5, 4, 8, 8>
+#define GDM_L7_7 launch7_p<7, 2, 8, 8>
+#define GDM_L7_9 launch7_p<9, 2, 8, 8>
+#define GDM_CAT_(a, b) a##b
+#define GDM_CAT(a, b) GDM_CAT_(a, b)
+#if defined(GDM_STENCIL_PART)
+hipError_t GDM_CAT(launch8_part, GDM_STENCIL_PART)(int bk, const StencilArgs &a, const TailReq &tail, hipStream_t st) {
+  return GDM_CAT(GDM_L8_, GDM_STENCIL_PART)(bk, a, tail, st);
+}
+hipError_t GDM_CAT(launch7_part, GDM_STENCIL_PART)(int bk, const StencilArgs &a, hipStream_t st) {
+  return GDM_CAT(GDM_L7_, GDM_STENCIL_PART)(bk, a, st);
+}
+#elif defined(GDM_STENCIL_SPLIT)
+#define GDM_PART_DECL(P)                                                                        \
+  hipError_t launch8_part##P(int bk, const StencilArgs &a, const TailReq &tail, hipStream_t st); \
+  hipError_t launch7_part##P(int bk, const StencilArgs &a, hipStream_t st);
+GDM_PART_DECL(1) GDM_PART_DECL(3) GDM_PART_DECL(5) GDM_PART_DECL(7) GDM_PART_DECL(9)
+#define GDM_LAUNCH8(P) launch8_part##P
+#define GDM_LAUNCH7(P) launch7_part##P
+#else
+#define GDM_LAUNCH8(P) GDM_L8_##P
+#define GDM_LAUNCH7(P) GDM_L7_##P
+#endif
+
 }  // namespace gdmk
 
+#ifndef GDM_STENCIL_PART
 extern "C" hipError_t gdmk_launch_stencil8(int p, int bk, const gdmk::StencilArgs &a, const gdmk::FaceArgs *tail_faces,
                                            int n_tail, unsigned long long *counter, bool *tail_ran,
                                            hipStream_t st) {
@@ -1985,19 +2026,19 @@ extern "C" hipError_t gdmk_launch_stencil8(int p, int bk, const gdmk::StencilArg
   hipError_t e = hipErrorInvalidValue;
   switch (p) {
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 1
-    case 1: e = launch8_p<1, 4, 8, 8, 3>(bk, a, tail, st); break;
+    case 1: e = GDM_LAUNCH8(1)(bk, a, tail, st); break;
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 3
-    case 3: e = launch8_p<3, 4, 8, 8, 3>(bk, a, tail, st); break;
+    case 3: e = GDM_LAUNCH8(3)(bk, a, tail, st); break;
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 5
-    case 5: e = launch8_p<5, GDM_R5, GDM_NC5, GDM_NP5, GDM_PF5>(bk, a, tail, st); break;
+    case 5: e = GDM_LAUNCH8(5)(bk, a, tail, st); break;
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 7
-    case 7: e = launch8_p<7, GDM_R7, GDM_NC7, GDM_NP7, GDM_PF7>(bk, a, tail, st); break;
+    case 7: e = GDM_LAUNCH8(7)(bk, a, tail, st); break;
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 9
-    case 9: e = launch8_p<9, 2, 8, 8, 3>(bk, a, tail, st); break;
+    case 9: e = GDM_LAUNCH8(9)(bk, a, tail, st); break;
 #endif
     default: break;
   }
@@ -2031,19 +2072,19 @@ extern "C" hipError_t gdmk_launch_stencil(int p, int bk, const gdmk::StencilArgs
   using namespace gdmk;
   switch (p) {
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 1
-    case 1: return launch7_p<1, 4, 8, 8>(bk, a, st);
+    case 1: return GDM_LAUNCH7(1)(bk, a, st);
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 3
-    case 3: return launch7_p<3, 4, 8, 8>(bk, a, st);
+    case 3: return GDM_LAUNCH7(3)(bk, a, st);
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 5
-    case 5: return launch7_p<5, 4, 8, 8>(bk, a, st);
+    case 5: return GDM_LAUNCH7(5)(bk, a, st);
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 7
-    case 7: return launch7_p<7, 2, 8, 8>(bk, a, st);
+    case 7: return GDM_LAUNCH7(7)(bk, a, st);
 #endif
 #if !defined(GDM_ONLY_P) || GDM_ONLY_P == 9
-    case 9: return launch7_p<9, 2, 8, 8>(bk, a, st);
+    case 9: return GDM_LAUNCH7(9)(bk, a, st);
 #endif
     
     default: return hipErrorInvalidValue;
@@ -2214,3 +2255,4 @@ extern "C" hipError_t gdmk_launch_zero(int64_t n, double *y, hipStream_t st) {
   hipLaunchKernelGGL(zero_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, y);
   return hipGetLastError();
 }
+#endif  // !GDM_STENCIL_PART

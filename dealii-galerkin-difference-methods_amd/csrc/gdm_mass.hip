@@ -912,8 +912,46 @@ hipError_t launch_mass3_rk_p(const double *src, int len, int64_t n_lines, const 
 
 }  // namespace
 
+// The single-sweep kernels of one degree take minutes to compile, so the build
+// compiles this file once per degree and entry point, side by side: a unit
+// built with -DGDM_MASS_PART=<p> holds only mass3_part<p> (the kernels of
+// gdmk_launch_mass3 at that degree), one built with -DGDM_MASS_RK_PART=<p>
+// only mass3_rk_part<p> (those of gdmk_launch_mass3_rk); the main unit, built
+// with -DGDM_MASS_SPLIT, holds everything else and calls them.  With none of
+// the macros one unit holds it all.
+#define GDM_CAT_(a, b) a##b
+#define GDM_CAT(a, b) GDM_CAT_(a, b)
+#define GDM_MASS3_ARGS                                                                                          \
+  int dir_kind, const double *src, double *dst, int len, int64_t stride, int64_t n_lines, int64_t A, int64_t B, \
+      const double *lrow, const double *urow, const double *invd, const double *cst, int row_lo, int row_hi,    \
+      int allow_segments, hipStream_t st
+#define GDM_MASS3_RK_ARGS                                                                                     \
+  const double *src, int len, int64_t n_lines, const double *lrow, const double *urow, const double *invd,    \
+      const double *cst, int row_lo, int row_hi, const RkOut &rk, hipStream_t st
+#if defined(GDM_MASS_PART)
+hipError_t GDM_CAT(mass3_part, GDM_MASS_PART)(GDM_MASS3_ARGS) {
+  return launch_mass3_p<GDM_MASS_PART>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo,
+                                       row_hi, allow_segments, st);
+}
+#elif defined(GDM_MASS_RK_PART)
+hipError_t GDM_CAT(mass3_rk_part, GDM_MASS_RK_PART)(GDM_MASS3_RK_ARGS) {
+  return launch_mass3_rk_p<GDM_MASS_RK_PART>(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
+}
+#elif defined(GDM_MASS_SPLIT)
+#define GDM_MASS_PART_DECL(P)                  \
+  hipError_t mass3_part##P(GDM_MASS3_ARGS); \
+  hipError_t mass3_rk_part##P(GDM_MASS3_RK_ARGS);
+GDM_MASS_PART_DECL(3) GDM_MASS_PART_DECL(5) GDM_MASS_PART_DECL(7)
+#define GDM_MASS3(P) mass3_part##P
+#define GDM_MASS3_RK(P) mass3_rk_part##P
+#else
+#define GDM_MASS3(P) launch_mass3_p<P>
+#define GDM_MASS3_RK(P) launch_mass3_rk_p<P>
+#endif
+
 }  // namespace gdmk
 
+#if !defined(GDM_MASS_PART) && !defined(GDM_MASS_RK_PART)
 extern "C" hipError_t gdmk_launch_mass3_rk(int p, const double *src, int len, int64_t n_lines, const double *lrow,
                                           const double *urow, const double *invd, const double *cst, int row_lo,
                                           int row_hi, const gdmk::RkOut &rk, hipStream_t st) {
@@ -923,9 +961,9 @@ extern "C" hipError_t gdmk_launch_mass3_rk(int p, const double *src, int len, in
   if (len % 2 != 0 || !al16(src) || !al16(rk.acc_in) || !al16(rk.acc_out) || (rk.Y && (!al16(rk.y) || !al16(rk.Y))))
     return hipErrorNotSupported;
   switch (p) {
-    case 3: return launch_mass3_rk_p<3>(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
-    case 5: return launch_mass3_rk_p<5>(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
-    case 7: return launch_mass3_rk_p<7>(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
+    case 3: return GDM_MASS3_RK(3)(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
+    case 5: return GDM_MASS3_RK(5)(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
+    case 7: return GDM_MASS3_RK(7)(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
     default: return hipErrorNotSupported;
   }
 }
@@ -952,9 +990,9 @@ extern "C" hipError_t gdmk_launch_mass3(int p, int dir_kind, const double *src, 
   using namespace gdmk;
   if (n_lines <= 0 || len <= 0) return hipSuccess;
   switch (p) {
-    case 3: return launch_mass3_p<3>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
-    case 5: return launch_mass3_p<5>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
-    case 7: return launch_mass3_p<7>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
+    case 3: return GDM_MASS3(3)(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
+    case 5: return GDM_MASS3(5)(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
+    case 7: return GDM_MASS3(7)(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
     default: return hipErrorInvalidValue;
   }
 }
@@ -977,3 +1015,4 @@ extern "C" hipError_t gdmk_launch_mass_lines(int p, int dir_kind, const double *
     default: return hipErrorInvalidValue;
   }
 }
+#endif  // not a per-degree unit

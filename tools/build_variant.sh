@@ -19,12 +19,12 @@ if [ "${BUILD_CAPI:-0}" = 1 ]; then
   /opt/rocm/bin/hipcc $F -x hip -c $C/gdm_capi.cpp -o $O/capi.o || exit 1
   CAPI=$O/capi.o
 fi
-MASS=$B/gdm_mass.o
+MASS="$B/gdm_mass.o $B/gdm_mass3_*.o"  # the in-tree build's main mass unit + its per-degree units
 if [ "${BUILD_MASS:-0}" = 1 ]; then
   /opt/rocm/bin/hipcc $F -c $C/gdm_mass.hip -o $O/mass.o || exit 1
   MASS=$O/mass.o
 fi
-KERN=$B/gdm_kernels.o
+KERN="$B/gdm_kernels.o $B/gdm_stencil_p*.o"  # the in-tree build's main unit + one unit per degree
 if [ "${BUILD_KERNELS:-1}" = 1 ]; then
   /opt/rocm/bin/hipcc $F -c $C/gdm_kernels.hip -o $O/kernels.o || exit 1
   KERN=$O/kernels.o
