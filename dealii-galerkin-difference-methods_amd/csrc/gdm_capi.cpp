@@ -21,6 +21,7 @@
 #include "gdm_post.h"
 #include "gdm_rk.h"
 #include "gdm_setup.h"
+#include "gdm_varstencil.h"
 
 namespace {
 
@@ -171,6 +172,23 @@ struct gdm_op {
   std::vector<double> xq;
   gdm::Slab slab{};
   std::vector<void *> allocations;
+  // separable advection field (gdm_op_set_advection_field): the launch plan of
+  // the volume kernel and the per-face arguments, all device memory allocated
+  // when the field is set
+  struct Field {
+    bool active = false;
+    int n_terms = 0;
+    double scale[gdmk::VAR_MAX_TERMS];       // s_t (gdm_op_set_field_scale)
+    gdmk::VarArgs vol{};                     // src / dst / scale filled per apply
+    size_t lds = 0;
+    std::vector<gdmk::VarFaceArgs> faces;    // u / bc / dst / coef filled per apply
+    std::vector<int64_t> face_bc_offset;
+    // per face and face term: the term and sign * f_normal(end) (coef = that * s_t)
+    std::vector<std::vector<int>> face_term;
+    std::vector<std::vector<double>> face_end;
+    std::vector<void *> allocations;
+  } field;
+  bool cut_inner = false;  // the inner operator of a gdm_cut_advection handle
 };
 
 namespace {
@@ -178,6 +196,7 @@ namespace {
 void free_op(gdm_op *op) {
   if (!op) return;
   for (void *ptr : op->allocations) (void)hipFree(ptr);
+  for (void *ptr : op->field.allocations) (void)hipFree(ptr);
   if (op->own_stream) (void)hipStreamDestroy(op->own_stream);
   delete op;
 }
@@ -1473,6 +1492,204 @@ void any_stencil(gdm_op *op, bool mass, const double *src, double *dst) {
     hip_check(launch_stencil(op, mass, src, dst), "stencil launch");
 }
 
+
+// ---- separable advection field (gdm_varstencil.hip) -------------------------
+
+// the box-face term of every face of a field operator, face by face on the
+// operator's stream (src NULL: the inflow data alone; bc NULL: u+ = 0)
+void field_faces(gdm_op *op, const double *src, double *dst, const double *bc) {
+  gdm_op::Field &fl = op->field;
+  for (size_t i = 0; i < fl.faces.size(); ++i) {
+    gdmk::VarFaceArgs f = fl.faces[i];
+    f.u = src;
+    f.bc = bc ? bc + fl.face_bc_offset[i] : nullptr;
+    f.dst = dst;
+    for (int k = 0; k < f.n_terms; ++k) f.coef[k] = fl.face_end[i][k] * fl.scale[fl.face_term[i][k]];
+    hip_check(gdmk::launch_var_face(op->p, f, op->stream), "field face launch");
+  }
+}
+
+void field_apply(gdm_op *op, const double *src, double *dst, const double *bc) {
+  gdm_op::Field &fl = op->field;
+  gdmk::VarArgs a = fl.vol;
+  a.src = src;
+  a.dst = dst;
+  for (int t = 0; t < fl.n_terms; ++t) a.scale[t] = fl.scale[t];
+  hip_check(gdmk::launch_var_volume(op->p, a, fl.lds, op->stream), "field volume launch");
+  field_faces(op, src, dst, bc);
+}
+
+// host checks shared by the pure-host field functions; 0 = ok
+int check_field_mesh(const gdm_mesh_desc *mesh, int axis) {
+  if (!mesh) return fail(GDM_ERR_ARG, "mesh is NULL");
+  const int dim = mesh->dim, p = mesh->fe_degree;
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (p < 1 || p > 9 || p % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (axis < 0 || axis >= dim) return fail(GDM_ERR_ARG, "axis outside [0, dim)");
+  if (mesh->n_subdivisions[axis] < p) return fail(GDM_ERR_ARG, "n_subdivisions must be >= fe_degree");
+  if (!(mesh->hi[axis] > mesh->lo[axis])) return fail(GDM_ERR_ARG, "empty box");
+  return GDM_OK;
+}
+
+// Build the launch plan, tables and scratch of a field into `nf` (every
+// device allocation is recorded in nf.allocations as it is made).
+void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::Field &nf) {
+  const int p = op->p, W = 2 * p + 1, n1 = p + 1;
+  auto up = [&](const std::vector<double> &h) {
+    double *d = dev_upload(h);
+    nf.allocations.push_back(d);
+    return d;
+  };
+  nf.n_terms = n_terms;
+  for (int t = 0; t < gdmk::VAR_MAX_TERMS; ++t) nf.scale[t] = 1.0;
+  // distinct 1D tables: (direction, M or C, factor array); direction -1 = identity
+  struct Table {
+    int d, which;
+    const double *f;
+    double *plain, *padded;
+  };
+  std::vector<Table> tabs;
+  auto table_id = [&](int d, int which, const double *f) {
+    if (d < 0) which = 0, f = nullptr;
+    for (size_t i = 0; i < tabs.size(); ++i)
+      if (tabs[i].d == d && tabs[i].which == which && tabs[i].f == f) return (int)i;
+    tabs.push_back(Table{d, which, f, nullptr, nullptr});
+    return (int)tabs.size() - 1;
+  };
+  auto host_band = [&](const Table &T) {
+    if (T.d < 0) {
+      gdm::Band I(1, p);
+      I(0, 0) = 1.0;
+      return I;
+    }
+    const unsigned nc = (unsigned)op->mesh.n_subdivisions[T.d];
+    const double h = (op->mesh.hi[T.d] - op->mesh.lo[T.d]) / nc;
+    // the samples start with the value at lo: the Gauss points follow
+    gdm::WeightedMatrices1D m = gdm::assemble_1d_weighted(p, nc, h, T.f ? T.f + 1 : nullptr);
+    return T.which ? m.C : m.M;
+  };
+  auto plain = [&](int id) {
+    if (!tabs[id].plain) tabs[id].plain = up(host_band(tabs[id]).a);
+    return (const double *)tabs[id].plain;
+  };
+  auto padded = [&](int id) {
+    if (!tabs[id].padded) {
+      const gdm::Band B = host_band(tabs[id]);
+      std::vector<double> t((size_t)(B.n + 2 * p) * W, 0.0);
+      std::copy(B.a.begin(), B.a.end(), t.begin() + (size_t)p * W);
+      tabs[id].padded = up(t);
+    }
+    return (const double *)tabs[id].padded;
+  };
+  gdmk::VarArgs &v = nf.vol;
+  v = gdmk::VarArgs{};
+  v.Nx = op->K[0];
+  v.Ny = op->K[1];
+  v.Nz = op->K[2];
+  v.n_terms = n_terms;
+  int xid[gdmk::VAR_MAX_TERMS], pair_x[gdmk::VAR_MAX_TERMS], pair_y[gdmk::VAR_MAX_TERMS];
+  for (int t = 0; t < n_terms; ++t) {
+    int id[3];
+    for (int ax = 0; ax < 3; ++ax) {
+      const int d = op->kdir[ax];
+      id[ax] = table_id(d, d == terms[t].component ? 1 : 0, d < 0 ? nullptr : terms[t].factor[d]);
+    }
+    int ix = 0;
+    while (ix < v.n_x && xid[ix] != id[0]) ++ix;
+    if (ix == v.n_x) {
+      xid[v.n_x] = id[0];
+      v.xtab[v.n_x++] = plain(id[0]);
+    }
+    int iv = 0;
+    while (iv < v.n_xy && !(pair_x[iv] == ix && pair_y[iv] == id[1])) ++iv;
+    if (iv == v.n_xy) {
+      pair_x[iv] = ix;
+      pair_y[iv] = id[1];
+      v.xy_x[iv] = ix;
+      v.ytab[iv] = plain(id[1]);
+      ++v.n_xy;
+    }
+    v.term_xy[t] = iv;
+    v.ztab[t] = padded(id[2]);
+  }
+  nf.lds = gdmk::var_volume_lds(p, v.n_x, v.n_xy);
+  if (nf.lds > 160 * 1024) throw std::runtime_error("advection field: the launch plan exceeds the LDS of a CU");
+  hip_check(gdmk::var_prepare(p, nf.lds), "advection field: LDS limit");
+
+  // faces: factor samples on the device, the shape table, scratch
+  struct Samples {
+    int d;
+    const double *f;
+    double *dev;
+  };
+  std::vector<Samples> smp;
+  auto samples = [&](int d, const double *f) -> const double * {
+    if (d < 0 || !f) return nullptr;
+    for (const Samples &s_ : smp)
+      if (s_.d == d && s_.f == f) return s_.dev + 1;
+    const size_t n = (size_t)op->mesh.n_subdivisions[d] * n1 + 2;
+    smp.push_back(Samples{d, f, up(std::vector<double>(f, f + n))});
+    return smp.back().dev + 1;
+  };
+  std::vector<double> xq, wq;
+  gdm::gauss_unit(n1, xq, wq);
+  std::vector<double> shape((size_t)std::max(1, p) * n1 * n1);
+  for (int cat = 0; cat < std::max(1, p); ++cat)
+    for (int l = 0; l < n1; ++l)
+      for (int q = 0; q < n1; ++q) shape[((size_t)cat * n1 + l) * n1 + q] = gdm::shape_1d(p, cat, l, xq[q], 0);
+  const double *shape_dev = up(shape);
+  int64_t gmax = 1, tmax = 1;
+  for (const Face &F : op->faces) {
+    gmax = std::max(gmax, (int64_t)F.t0.Q * F.t1.Q);
+    tmax = std::max(tmax, (int64_t)F.t0.n_nodes * F.t1.Q);
+  }
+  double *G = up(std::vector<double>((size_t)gmax, 0.0));
+  double *T = up(std::vector<double>((size_t)tmax, 0.0));
+  for (const Face &F : op->faces) {
+    gdmk::VarFaceArgs f{};
+    std::vector<int> fterm;
+    std::vector<double> fend;
+    for (int t = 0; t < n_terms; ++t) {
+      if (terms[t].component != F.d) continue;
+      const double *fn = terms[t].factor[F.d];
+      const size_t last = (size_t)op->mesh.n_subdivisions[F.d] * n1 + 1;
+      const double end = fn ? fn[F.side ? last : 0] : 1.0;
+      fterm.push_back(t);
+      fend.push_back(F.side ? end : -end);  // a.n
+      f.f0[f.n_terms] = samples(F.t0.dim_index, F.t0.dim_index < 0 ? nullptr : terms[t].factor[F.t0.dim_index]);
+      f.f1[f.n_terms] = samples(F.t1.dim_index, F.t1.dim_index < 0 ? nullptr : terms[t].factor[F.t1.dim_index]);
+      ++f.n_terms;
+    }
+    if (f.n_terms == 0) continue;  // a.n = 0 on this face
+    f.G = G;
+    f.T = T;
+    f.Q0 = F.t0.Q;
+    f.Q1 = F.t1.Q;
+    f.nc0 = F.t0.dim_index < 0 ? 0 : op->mesh.n_subdivisions[F.t0.dim_index];
+    f.nc1 = F.t1.dim_index < 0 ? 0 : op->mesh.n_subdivisions[F.t1.dim_index];
+    f.n0 = F.t0.n_nodes;
+    f.n1 = F.t1.n_nodes;
+    f.base = F.base;
+    f.stride0 = F.t0.stride;
+    f.stride1 = F.t1.stride;
+    f.shape = shape_dev;
+    f.qs0 = F.t0.qs;
+    f.qc0 = F.t0.qc;
+    f.w0 = F.t0.w;
+    f.wmax0 = F.t0.wmax;
+    f.qs1 = F.t1.qs;
+    f.qc1 = F.t1.qc;
+    f.w1 = F.t1.w;
+    f.wmax1 = F.t1.wmax;
+    nf.faces.push_back(f);
+    nf.face_bc_offset.push_back(F.offset);
+    nf.face_term.push_back(fterm);
+    nf.face_end.push_back(fend);
+  }
+  nf.active = true;
+}
+
+const char *kFieldPlanes = "gdm_apply_planes: not with a separable advection field (gdm_op_set_advection_field)";
 }  // namespace
 
 int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const double *bc_values) {
@@ -1480,7 +1697,9 @@ int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const doub
   if (op->layout.n_owned > 0 && (!src_local || !dst_owned)) return fail(GDM_ERR_ARG, "NULL vector");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
-  if (op->concurrent && !op->mesh.periodic) {
+  if (op->field.active) {
+    field_apply(op, src_local, dst_owned, bc_values);
+  } else if (op->concurrent && !op->mesh.periodic) {
     apply_with_faces(op, op->kind == GDM_OP_MASS, src_local, dst_owned, bc_values);
   } else {
     any_stencil(op, op->kind == GDM_OP_MASS, src_local, dst_owned);
@@ -1496,6 +1715,7 @@ int gdm_apply_planes(gdm_op *op, const double *src_local, double *dst_owned, int
   if (op->part_axis != 2 && (plane_begin > op->layout.owned_plane_begin || plane_end < op->layout.owned_plane_end))
     return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: plane sub-ranges need a 3D mesh");
   if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: periodic constraints");
+  if (op->field.active) return fail(GDM_ERR_UNSUPPORTED, kFieldPlanes);
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
   hip_check(launch_stencil(op, op->kind == GDM_OP_MASS, src_local, dst_owned, plane_begin, plane_end),
@@ -1509,6 +1729,7 @@ int gdm_apply_planes2(gdm_op *op, const double *src_local, double *dst_owned, in
   if (op->layout.n_owned > 0 && (!src_local || !dst_owned)) return fail(GDM_ERR_ARG, "NULL vector");
   if (op->part_axis != 2) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: plane ranges need a 3D mesh");
   if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: periodic constraints");
+  if (op->field.active) return fail(GDM_ERR_UNSUPPORTED, kFieldPlanes);
   // clip both ranges to the owned planes first (a first range in
   // the ghost planes must not drop the second), then test overlap and emptiness
   {
@@ -1548,9 +1769,85 @@ int gdm_add_boundary_data(gdm_op *op, const double *bc_values, double *dst_owned
   if (op->layout.n_bc_points > 0 && (!bc_values || !dst_owned)) return fail(GDM_ERR_ARG, "NULL vector");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
-  launch_boundary_data(op, bc_values, dst_owned);
+  if (op->field.active)
+    field_faces(op, nullptr, dst_owned, bc_values);
+  else
+    launch_boundary_data(op, bc_values, dst_owned);
   return GDM_OK;
   GDM_GUARD_END
+}
+
+int gdm_field_points(const gdm_mesh_desc *mesh, int axis, double *x_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  if (!x_host) return fail(GDM_ERR_ARG, "x_host is NULL");
+  GDM_GUARD_BEGIN
+  const std::vector<double> x = gdm::field_points_1d(mesh->fe_degree, (unsigned)mesh->n_subdivisions[axis],
+                                                     mesh->lo[axis], mesh->hi[axis]);
+  std::copy(x.begin(), x.end(), x_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_field_matrix_1d(const gdm_mesh_desc *mesh, int axis, int which, const double *f, double *band_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  if (!band_host) return fail(GDM_ERR_ARG, "band_host is NULL");
+  if (which != 0 && which != 1) return fail(GDM_ERR_ARG, "which: 0 = M[f], 1 = C[f]");
+  GDM_GUARD_BEGIN
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  const double h = (mesh->hi[axis] - mesh->lo[axis]) / nc;
+  const gdm::WeightedMatrices1D m = gdm::assemble_1d_weighted(mesh->fe_degree, nc, h, f ? f + 1 : nullptr);
+  const gdm::Band &B = which ? m.C : m.M;
+  std::copy(B.a.begin(), B.a.end(), band_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_field_tile(int fe_degree, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (tile_x) *tile_x = gdmk::VAR_TX;
+  if (tile_y) *tile_y = gdmk::VAR_TY;
+  if (z_chunk) *z_chunk = gdmk::VAR_ZC;
+  return GDM_OK;
+}
+
+int gdm_op_set_advection_field(gdm_op *op, int n_terms, const gdm_field_term *terms) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_ADVECTION)
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_advection_field: advection operators only");
+  if (op->cut_inner)
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_advection_field: the cut-cell rows of a gdm_cut_advection handle "
+                                     "are assembled for its constant field");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_advection_field: single rank only");
+  if (n_terms < 0 || n_terms > GDM_FIELD_MAX_TERMS)
+    return fail(GDM_ERR_ARG, "gdm_op_set_advection_field: n_terms must be in [0, GDM_FIELD_MAX_TERMS]");
+  if (n_terms > 0 && !terms) return fail(GDM_ERR_ARG, "gdm_op_set_advection_field: terms is NULL");
+  for (int t = 0; t < n_terms; ++t)
+    if (terms[t].component < 0 || terms[t].component >= op->dim)
+      return fail(GDM_ERR_ARG, "gdm_op_set_advection_field: component must be in [0, dim)");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  gdm_op::Field nf;
+  if (n_terms > 0) {
+    try {
+      build_field(op, n_terms, terms, nf);
+    } catch (...) {
+      for (void *ptr : nf.allocations) (void)hipFree(ptr);
+      throw;
+    }
+  }
+  // applies in flight read the old tables
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  for (void *ptr : op->field.allocations) (void)hipFree(ptr);
+  op->field = std::move(nf);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_op_set_field_scale(gdm_op *op, const double *s) {
+  if (!op || !s) return fail(GDM_ERR_ARG, "NULL argument");
+  if (!op->field.active) return fail(GDM_ERR_STATE, "gdm_op_set_field_scale: no advection field is set");
+  for (int t = 0; t < op->field.n_terms; ++t) op->field.scale[t] = s[t];
+  return GDM_OK;
 }
 
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned) {
@@ -1984,7 +2281,7 @@ const double *fill_stage_boundary(gdm_op *op, int fn_kind, const double *params,
   // only the inflow faces: the others' values are never read (scale 0)
   int faces[gdmk::BcStage::kMaxFaces], n = 0;
   for (size_t fi = 0; fi < op->faces.size(); ++fi)
-    if (op->faces[fi].scale != 0.0) faces[n++] = (int)fi;
+    if (op->faces[fi].scale != 0.0 || op->field.active) faces[n++] = (int)fi;  // a field has no fixed inflow faces
   hip_check(gdmk_launch_bc_stage_fill(stage, faces, n, op->bc_stage_vals, st), "bc stage fill");
   return op->bc_stage_vals;
 }
@@ -2005,7 +2302,9 @@ int gdm_apply_bc_fn(gdm_op *op, const double *src_local, double *dst_owned, int 
   // pass), then gdm_apply with them; a side-stream launch would wait for the
   // interior launch's workgroups (one per CU, all of its LDS) to drain
   const double *bc = fill_stage_boundary(op, fn_kind, params, n_params, t_g, alpha, t_k, op->stream);
-  if (op->concurrent && !op->mesh.periodic) {
+  if (op->field.active) {
+    field_apply(op, src_local, dst_owned, bc);
+  } else if (op->concurrent && !op->mesh.periodic) {
     apply_with_faces(op, false, src_local, dst_owned, bc);
   } else {
     any_stencil(op, false, src_local, dst_owned);
@@ -2025,7 +2324,10 @@ int gdm_add_boundary_fn(gdm_op *op, double *dst_owned, int fn_kind, const double
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
   const double *bc = fill_stage_boundary(op, fn_kind, params, n_params, t_g, alpha, t_k, op->stream);
-  launch_boundary_data(op, bc, dst_owned);
+  if (op->field.active)
+    field_faces(op, nullptr, dst_owned, bc);
+  else
+    launch_boundary_data(op, bc, dst_owned);
   return GDM_OK;
   GDM_GUARD_END
 }
@@ -2467,6 +2769,7 @@ int gdm_cut_advection_create2(int fe_degree, int n_subdivisions, double left, do
       delete c;
       return rc;
     }
+    c->op->cut_inner = true;  // the cut rows C, F are assembled for the constant field
     gdmh_cut_adv_info(c->host, &c->n_dofs, &c->n_bc, c->cells, &c->bw);
     const int64_t *crp, *frp;
     const uint32_t *cci, *fci;

@@ -120,6 +120,60 @@ Matrices1D assemble_1d(int p, unsigned n_cells, double h) {
   return m;
 }
 
+WeightedMatrices1D assemble_1d_weighted(int p, unsigned n_cells, double h, const double *f) {
+  if (n_cells < (unsigned)p) throw std::invalid_argument("n_subdivisions must be >= fe_degree");
+  const int n1 = p + 1, N = int(n_cells) + 1;
+  WeightedMatrices1D m{Band(N, p), Band(N, p)};
+  std::vector<double> xq, wq;
+  gauss_unit(n1, xq, wq);
+  const int ncat = std::max(1, p);
+  std::vector<double> val((size_t)ncat * n1 * n1), der((size_t)ncat * n1 * n1);
+  for (int cat = 0; cat < ncat; ++cat)
+    for (int i = 0; i < n1; ++i)
+      for (int q = 0; q < n1; ++q) {
+        val[((size_t)cat * n1 + i) * n1 + q] = shape_1d(p, cat, i, xq[q], 0);
+        der[((size_t)cat * n1 + i) * n1 + q] = shape_1d(p, cat, i, xq[q], 1) / h;
+      }
+  for (unsigned c = 0; c < n_cells; ++c) {
+    const int cat = int(category(c, p, n_cells));
+    const int off = int(box_offset(c, p, n_cells));
+    const double *v = &val[(size_t)cat * n1 * n1];
+    const double *g = &der[(size_t)cat * n1 * n1];
+    const double *fc = f ? f + (size_t)c * n1 : nullptr;
+    for (int i = 0; i < n1; ++i)
+      for (int j = 0; j < n1; ++j) {
+        double mm = 0, cc = 0;
+        for (int q = 0; q < n1; ++q) {
+          // f == 1 takes assemble_1d's arithmetic, so its bits
+          const double jxw = wq[q] * h;
+          if (fc) {
+            mm += v[i * n1 + q] * v[j * n1 + q] * (jxw * fc[q]);
+            cc += g[i * n1 + q] * v[j * n1 + q] * (jxw * fc[q]);
+          } else {
+            mm += v[i * n1 + q] * v[j * n1 + q] * jxw;
+            cc += g[i * n1 + q] * v[j * n1 + q] * jxw;
+          }
+        }
+        m.M(off + i, off + j) += mm;
+        m.C(off + i, off + j) += cc;
+      }
+  }
+  return m;
+}
+
+std::vector<double> field_points_1d(int p, unsigned n_cells, double lo, double hi) {
+  const int n1 = p + 1;
+  std::vector<double> xq, wq, x;
+  gauss_unit(n1, xq, wq);
+  const double h = (hi - lo) / n_cells;
+  x.reserve((size_t)n_cells * n1 + 2);
+  x.push_back(lo);
+  for (unsigned c = 0; c < n_cells; ++c)
+    for (int q = 0; q < n1; ++q) x.push_back(lo + (c + xq[q]) * h);
+  x.push_back(hi);
+  return x;
+}
+
 void cholesky_band(const Band &M, std::vector<double> &lrow, std::vector<double> &inv_diag) {
   const int n = M.n, hb = M.hb, wl = hb + 1;
   lrow.assign((size_t)n * wl, 0.0);

@@ -78,6 +78,16 @@ class Layout(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FieldTerm(ctypes.Structure):
+    """gdm_field_term: one term s_t f_0(x_0) f_1(x_1) f_2(x_2) of a velocity component"""
+    _fields_ = [
+        ("component", ctypes.c_int32),
+        ("factor", ctypes.c_void_p * 3),
+    ]
+
+
+FIELD_MAX_TERMS = 8
+
 _lib = None
 
 
@@ -129,6 +139,12 @@ def load():
         "gdm_add_boundary_data": [P, P, P],
         "gdm_apply_planes": [P, P, P, i32, i32],
         "gdm_apply_planes2": [P, P, P, i32, i32, i32, i32],
+        "gdm_field_points": [ctypes.POINTER(MeshDesc), i32, P],
+        "gdm_field_matrix_1d": [ctypes.POINTER(MeshDesc), i32, i32, P, P],
+        "gdm_field_tile": [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                           ctypes.POINTER(ctypes.c_int)],
+        "gdm_op_set_advection_field": [P, i32, P],
+        "gdm_op_set_field_scale": [P, P],
         "gdm_mass_apply": [P, P, P],
         "gdm_mass_solve": [P, P, P],
         "gdm_mass_solve_rk": [P, P, d, P, P, d, P, P],
@@ -240,6 +256,47 @@ def mesh_desc(dim, fe_degree, n_subdivisions, lo=0.0, hi=1.0, n_ranks=1, rank=0,
         m.hi[d] = float(hi) if d < dim else 1.0
     m.n_ranks, m.rank, m.periodic = n_ranks, rank, periodic
     return m
+
+
+def field_points(mesh, axis):
+    """The n_sub (p+1) + 2 abscissae at which a field factor along `axis` is
+    sampled: lo, the Gauss points cell by cell, hi (pure host, no GPU)."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("field_points: axis outside [0, dim)")
+    x = np.zeros(mesh.n_subdivisions[axis] * (mesh.fe_degree + 1) + 2)
+    check(load().gdm_field_points(ctypes.byref(mesh), int(axis), x.ctypes.data_as(ctypes.c_void_p)),
+          "gdm_field_points")
+    return x
+
+
+def field_matrix_1d(mesh, axis, which, f=None):
+    """Band [n_sub + 1][2p+1] of M[f] (which = 0) or C[f] (which = 1) along
+    `axis`; f sampled at field_points (None: f = 1).  Pure host, no GPU."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("field_matrix_1d: axis outside [0, dim)")
+    n = mesh.n_subdivisions[axis]
+    fp = None
+    if f is not None:
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.size != n * (mesh.fe_degree + 1) + 2:
+            raise GdmError("field_matrix_1d: f has %d samples, field_points has %d"
+                           % (f.size, n * (mesh.fe_degree + 1) + 2))
+        fp = f.ctypes.data_as(ctypes.c_void_p)
+    band = np.zeros((n + 1, 2 * mesh.fe_degree + 1))
+    check(load().gdm_field_matrix_1d(ctypes.byref(mesh), int(axis), int(which), fp,
+                                     band.ctypes.data_as(ctypes.c_void_p)), "gdm_field_matrix_1d")
+    return band
+
+
+def field_tile(fe_degree):
+    """(tile_x, tile_y, z_chunk) of the separable field's volume kernel, kernel axes"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_field_tile(int(fe_degree), *[ctypes.byref(v) for v in t]), "gdm_field_tile")
+    return tuple(v.value for v in t)
 
 
 def mass_spike_rounds(dim, fe_degree, n_subdivisions, n_ranks, lo=0.0, hi=1.0):

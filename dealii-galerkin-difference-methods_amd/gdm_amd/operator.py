@@ -142,6 +142,52 @@ class GdmOperator:
         check(self.lib.gdm_add_boundary_data(self.h, _ptr(bc_values), _ptr(dst_owned)), "gdm_add_boundary_data")
         return dst_owned
 
+    # -- separable advection field --------------------------------------------
+    def field_points(self, axis):
+        """Abscissae at which a field factor along `axis` is sampled
+        (gdm_field_points): lo, the Gauss points cell by cell, hi."""
+        return _capi.field_points(self.mesh, axis)
+
+    def set_advection_field(self, terms):
+        """a_d(x) = sum of the terms (component d, [f0, f1, f2]) of products
+        f0(x_0) f1(x_1) f2(x_2) (gdm_op_set_advection_field).  A factor is an
+        array sampled at field_points(axis), a callable evaluated there, or
+        None (= 1).  Terms that pass the same array object share its tables
+        and sweeps.  An empty list restores the constant field of the
+        constructor."""
+        terms = list(terms)
+        arr = (_capi.FieldTerm * max(len(terms), 1))()
+        keep = {}  # id(factor object) -> sampled array: object identity becomes pointer identity
+        for t, (comp, factors) in enumerate(terms):
+            arr[t].component = int(comp)
+            factors = list(factors) + [None] * (3 - len(factors))
+            for d in range(3):
+                f = factors[d]
+                if f is None or d >= self.dim:
+                    arr[t].factor[d] = None
+                    continue
+                if id(f) not in keep:
+                    x = self.field_points(d)
+                    v = np.array([f(xi) for xi in x], dtype=np.float64) if callable(f) else \
+                        np.ascontiguousarray(f, dtype=np.float64)
+                    if v.shape != x.shape:
+                        raise GdmError("set_advection_field: term %d factor %d has shape %s, field_points(%d) %s"
+                                       % (t, d, v.shape, d, x.shape))
+                    keep[id(f)] = (f, v)
+                arr[t].factor[d] = keep[id(f)][1].ctypes.data
+        check(self.lib.gdm_op_set_advection_field(self.h, len(terms), arr if terms else None),
+              "gdm_op_set_advection_field")
+        self.n_field_terms = len(terms)
+
+    def set_field_scale(self, s):
+        """the time factors s_t of the field's terms (gdm_op_set_field_scale):
+        used by every apply enqueued afterwards"""
+        s = [float(v) for v in s]
+        if len(s) != getattr(self, "n_field_terms", 0):
+            raise GdmError("set_field_scale: %d values for %d terms" % (len(s), getattr(self, "n_field_terms", 0)))
+        check(self.lib.gdm_op_set_field_scale(self.h, (ctypes.c_double * max(len(s), 1))(*s)),
+              "gdm_op_set_field_scale")
+
     def mass_apply(self, src_local, dst_owned):
         self._check_sizes(src_local, dst_owned)
         check(self.lib.gdm_mass_apply(self.h, _ptr(src_local), _ptr(dst_owned)), "gdm_mass_apply")

@@ -118,11 +118,15 @@ class AdvectionProblem:
     """advection problem.h:31-102 on one rank with a built-in boundary
     function (gdm_fn_kind) for g and dg/dt."""
 
-    def __init__(self, op, fn_kind, fn_params, carry_bc=False):
+    def __init__(self, op, fn_kind, fn_params, carry_bc=False, field_scale=None):
         if op.mesh.n_ranks != 1:
             raise GdmError("AdvectionProblem: single-rank driver")
         self.op, self.fn, self.prm = op, int(fn_kind), list(fn_params)
         self.carry_bc = bool(carry_bc)
+        # field_scale(t) -> the time factors s_t of the operator's separable field
+        # at time t: the reference's advection->set_time(time) before every
+        # compute_rhs (stiffness.h:339)
+        self.field_scale = field_scale
         import torch
 
         dev = "cuda:%d" % op.device
@@ -156,8 +160,13 @@ class AdvectionProblem:
             self.op.eval_boundary(self.fn, self.prm, t, 0, self.bc)
         return True
 
+    def _set_time(self, t):
+        if self.field_scale is not None:
+            self.op.set_field_scale(self.field_scale(t))
+
     def rhs(self, t, BC, U, kbc, ku):
         op = self.op
+        self._set_time(t)
         if op.n_bc_points:
             op.eval_boundary(self.fn, self.prm, t, 1, kbc)  # block(0) = dg/dt (stiffness.h:286-289)
         op.apply(U, ku, BC if op.n_bc_points else None)
@@ -171,6 +180,7 @@ class AdvectionProblem:
             stage = y
             for s in range(4):
                 alpha, t_k = (0.0, t) if s == 0 else (h * RK4_A[s - 1], t + RK4_C[s - 1] * h)
+                self._set_time(t + RK4_C[s] * h)
                 op.apply_bc_fn(stage, k, self.fn, self.prm, t, alpha, t_k)
                 last = s == 3
                 op.mass_solve_rk(k, h * RK4_B[s], y if s == 0 else acc, y if last else acc,

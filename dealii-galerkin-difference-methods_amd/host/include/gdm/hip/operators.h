@@ -278,6 +278,42 @@ class StiffnessMatrixOperator {
     for (int64_t i = 0; i < layout.n_bc_points; ++i) all_points_0[i] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
   }
 
+  // A separable, spatially varying advection field in place of the constant
+  // params.advection (gdm_op_set_advection_field, after reinit; single rank):
+  // a_d(x, t) = sum over the terms with component d of s_t(t) f_t0(x_0) ...
+  // f_t(dim-1)(x_(dim-1)) -- advection->value(x_q, d) of the reference
+  // (stiffness.h:395-406, 443, 510) for fields of that form.  factors[d] holds
+  // f_td sampled at field_points(d) (empty = 1); terms that pass the same
+  // vector object share its tables.  No terms: the constant field again.
+  struct FieldTerm {
+    int component = 0;
+    std::array<const std::vector<double> *, dim> factors{};
+  };
+
+  // abscissae at which a factor along direction d is sampled: lo, the Gauss
+  // points cell by cell, hi
+  std::vector<double> field_points(int d) const {
+    const gdm_mesh_desc &m = discretization.get_mesh();
+    std::vector<double> x((std::size_t)m.n_subdivisions[d] * (m.fe_degree + 1) + 2);
+    check(gdm_field_points(&m, d, x.data()), "gdm_field_points");
+    return x;
+  }
+
+  void set_advection_field(const std::vector<FieldTerm> &terms) {
+    std::vector<gdm_field_term> t(terms.size());
+    for (std::size_t i = 0; i < terms.size(); ++i) {
+      t[i].component = terms[i].component;
+      for (int d = 0; d < 3; ++d)
+        t[i].factor[d] = d < dim && terms[i].factors[d] && !terms[i].factors[d]->empty() ? terms[i].factors[d]->data()
+                                                                                            : nullptr;
+    }
+    check(gdm_op_set_advection_field(op, (int)t.size(), t.data()), "gdm_op_set_advection_field");
+  }
+
+  // the time factors s_t of the field's terms: advection->set_time(time)
+  // (stiffness.h:339) before a stage's compute_rhs
+  void set_field_scale(const std::vector<double> &s) { check(gdm_op_set_field_scale(op, s.data()), "gdm_op_set_field_scale"); }
+
   // boundary_block = false: block(0) is left empty (size 0), for drivers that
   // let the engine compute the stage boundary values (boundary_in_faces)
   void initialize_dof_vector(BlockVector &vec, bool boundary_block = true) const {

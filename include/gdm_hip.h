@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GDM_HIP_ABI_VERSION 15
+#define GDM_HIP_ABI_VERSION 16
 
 enum gdm_status {
   GDM_OK = 0,
@@ -148,11 +148,16 @@ typedef struct {
  *   GDM_OP_ADVECTION   : a_x, a_y, a_z               (constant field, see below)
  *   GDM_OP_CONVECTIVE  : a_x, a_y, a_z
  *   The reference evaluates advection->value(x_q, d) at every quadrature point
- *   (advection/stiffness.h:395-406, 443, 510); the engine's Kronecker form
- *   holds for a CONSTANT field only, which is what every reference preset uses
- *   (ConstantFunction, advection-app.cc:131-139).  A spatially varying field
- *   cannot be expressed through these params: a caller with one must keep the
- *   reference's cell loop (the engine cannot detect it, it only sees a[]).
+ *   (advection/stiffness.h:395-406, 443, 510).  The params give a CONSTANT
+ *   field, which is what every reference preset uses (ConstantFunction,
+ *   advection-app.cc:131-139).  A spatially varying field is expressible when
+ *   every component is a short sum of products of one-variable functions,
+ *   a_d(x, t) = sum_t s_t(t) f_t0(x_0) f_t1(x_1) f_t2(x_2) (solid-body rotation,
+ *   shear flows, the deformational swirl): gdm_op_set_advection_field below
+ *   replaces a[] by such a sum and the result equals the reference's cell loop
+ *   up to summation order.  A general Function<dim> without that structure is
+ *   still not expressible: a caller with one must keep the reference's cell
+ *   loop (the engine cannot detect it, it only sees what it is given).
  *   GDM_OP_WAVE        : [nitsche_parameter]         (> 0 enables box Nitsche,
  *                        function_domain_dbc; absent / <= 0 = natural BC) */
 int gdm_last_error(char *buf, size_t len);
@@ -199,6 +204,61 @@ int gdm_apply_planes2(gdm_op *op, const double *src_local, double *dst_owned, in
 /* dst_owned += inflow boundary-data term only (the bc part of gdm_apply,
  * advection/stiffness.h:520-529 with a.n < 0); no-op for other kinds */
 int gdm_add_boundary_data(gdm_op *op, const double *bc_values, double *dst_owned);
+/* ------------------------------------------------------------------------
+ * Separable advection field (ABI 16): a_d(x, t) = sum over the terms t with
+ * component d of s_t(t) f_t0(x_0) f_t1(x_1) f_t2(x_2) on a GDM_OP_ADVECTION
+ * operator -- advection->value(x_q, d) after advection->set_time(t)
+ * (advection/stiffness.h:339, 395-406, 443, 510) for fields of that form.
+ * Tensor Gauss quadrature of (a u, grad v) factorises exactly: each term is
+ * A_x (x) A_y (x) A_z with the banded 1D matrices C[f] (along the term's
+ * component: sum_q w_q f(x_q) phi_i'(x_q) phi_j(x_q)) and M[f] (elsewhere:
+ * sum_q w_q f(x_q) phi_i(x_q) phi_j(x_q)); the box-face term takes a.n at
+ * every face quadrature point from the same samples.
+ *
+ *   gdm_field_points     pure host (no device, no op): the n_sub (p+1) + 2
+ *                        abscissae along `axis` at which a factor is sampled:
+ *                        lo, the Gauss points cell by cell, hi (the two end
+ *                        values give the normal flux on the box faces)
+ *   gdm_field_matrix_1d  pure host: the band [n_sub + 1][2p+1] (entry [i][k] =
+ *                        A(i, i - p + k)) of M[f] (which = 0) or C[f] (which =
+ *                        1) the engine uses along `axis`; f sampled at
+ *                        gdm_field_points (NULL: f = 1)
+ *   gdm_op_set_advection_field
+ *                        builds and uploads every table and scratch buffer of
+ *                        the field and replaces the constant a[] of
+ *                        gdm_op_create; calling it again replaces the field
+ *                        (it waits for the operator's stream first);
+ *                        n_terms = 0 restores the constant field and its code
+ *                        path, bit for bit.  factor[d] are HOST arrays sampled
+ *                        at gdm_field_points(d) (NULL = 1; entries d >= dim are
+ *                        ignored); at most GDM_FIELD_MAX_TERMS terms; terms that
+ *                        pass the same array (pointer identity) share its
+ *                        tables and sweeps.  The arrays are copied.
+ *   gdm_op_set_field_scale
+ *                        the time factors s_t (default 1): host values, not
+ *                        baked into the tables; every apply enqueued after the
+ *                        call uses them (an RK driver calls it per stage), a
+ *                        captured graph keeps the values of its capture.
+ * With a field gdm_apply (with and without bc_values), gdm_add_boundary_data,
+ * gdm_apply_bc_fn, gdm_add_boundary_fn and gdm_time_op work as before; the mass
+ * entry points do not depend on a.  GDM_ERR_UNSUPPORTED: n_ranks > 1, a
+ * non-advection operator, the inner operator of a gdm_cut_advection handle,
+ * and gdm_apply_planes / gdm_apply_planes2 while a field is set.  GDM_ERR_ARG:
+ * n_terms outside [0, GDM_FIELD_MAX_TERMS], component outside [0, dim).
+ * gdm_field_tile: the (x, y) tile and the z chunk of the field's volume kernel
+ * in kernel axes (pure host; for tests and sizing).
+ * ---------------------------------------------------------------------- */
+#define GDM_FIELD_MAX_TERMS 8
+typedef struct {
+  int32_t component;       /* the velocity component this term belongs to */
+  const double *factor[3]; /* host arrays at gdm_field_points; NULL = 1     */
+} gdm_field_term;
+int gdm_field_points(const gdm_mesh_desc *mesh, int axis, double *x_host);
+int gdm_field_matrix_1d(const gdm_mesh_desc *mesh, int axis, int which, const double *f, double *band_host);
+int gdm_field_tile(int fe_degree, int *tile_x, int *tile_y, int *z_chunk);
+int gdm_op_set_advection_field(gdm_op *op, int n_terms, const gdm_field_term *terms);
+int gdm_op_set_field_scale(gdm_op *op, const double *s);
+
 /* dst_owned = M src_local */
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned);
 /* x_owned = M^-1 rhs_owned (exact Kronecker inverse; single rank; not with
