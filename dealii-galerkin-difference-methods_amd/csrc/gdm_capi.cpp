@@ -18,6 +18,7 @@
 #include "../../include/gdm_hip.h"
 #include "gdm_coeffs.h"
 #include "gdm_kernels.h"
+#include "gdm_periodic.h"
 #include "gdm_post.h"
 #include "gdm_rk.h"
 #include "gdm_setup.h"
@@ -110,6 +111,18 @@ struct SpikeTables {
   int k_begin = 0, k_end = 0;  // planes the correction touches
 };
 
+// Exact mass inverse with periodicity constraints (gdm_mass_solve_periodic):
+// per periodic direction the line tables of A~ = blockdiag(A, 1) (kernel axis
+// of the direction) and the rank-2 Woodbury correction (gdm_periodic.hip); w =
+// the gather scratch [2][most lines of a periodic direction].  All of it is
+// built by gdm_op_create, so the first solve may run inside a stream capture.
+struct PeriodicMass {
+  LineTables tab[3];           // by kernel axis
+  const LineTables *axis_tab[3] = {nullptr, nullptr, nullptr};
+  gdmk::PeriodicDir dir[3]{};  // by reference direction
+  double *w = nullptr;
+};
+
 struct gdm_op {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -146,6 +159,7 @@ struct gdm_op {
   std::vector<double> cst3_host[3];
   double *bc_tab = nullptr;  // gdm_eval_boundary: per-face 1D factor tables
   SpikeTables spike;         // distributed mass inverse (n_ranks > 1)
+  PeriodicMass pmass;        // exact mass inverse with periodicity constraints
   // gdm_error_norms: shape values per category, per-workgroup partials, result
   double *err_S = nullptr, *err_partial = nullptr;
   static constexpr int n_err_partial = 1024;
@@ -964,6 +978,144 @@ void band_chol_solve(const std::vector<double> &lrow, const std::vector<double> 
   }
 }
 
+// Host tables of one periodic direction (gdm_periodic.hip).  With A =
+// M[0:N-1, 0:N-1], U = [e_0, m], m = M[0:N-1, N-1] and S = [[M[N-1,N-1], 1],
+// [1, 0]] the condensed matrix is M_per = A + U S U^T and
+//   M_per^-1 b = g - T (U^T g),  g = A^-1 b,  T = Z (S^-1 + U^T Z)^-1,  Z = A^-1 U.
+// The 2 x 2 capacitance matrix is badly scaled (its condition grows like
+// 1 / h^2): the second column of U is scaled by 1 / max|m| and the 2 x 2
+// inverse taken in long double.  At = blockdiag(A, 1): its Cholesky rows are
+// M's except the last one, so every line kernel runs it at line length N and
+// passes the last entry through.  The correction skips the longest run of rows
+// k >= 1 with max(|T[k][0]|, |T[k][1]| max|m|) <= 1e-18 (the SPIKE path's rule,
+// scale-free); rows [0, rows_lo) and [N-1-rows_hi, N-1) remain.
+struct PeriodicTables1D {
+  gdm::Band At;
+  std::vector<double> T, m;  // [N-1][2], [p]
+  int rows_lo = 0, rows_hi = 0;
+};
+PeriodicTables1D periodic_tables_1d(const gdm::Band &M, int p) {
+  const int N = M.n, n = N - 1;
+  if (n < p) throw std::invalid_argument("periodic tables: fewer than p free vertices");
+  PeriodicTables1D r;
+  r.At = gdm::Band(N, p);
+  gdm::Band A(n, p);
+  for (int i = 0; i < n; ++i)
+    for (int j = std::max(0, i - p); j <= std::min(n - 1, i + p); ++j) A(i, j) = r.At(i, j) = M(i, j);
+  r.At(n, n) = 1.0;
+  r.m.resize((size_t)p);
+  double s = 0.0;
+  for (int j = 0; j < p; ++j) {
+    r.m[(size_t)j] = M(n - p + j, n);
+    s = std::max(s, std::abs(r.m[(size_t)j]));
+  }
+  if (!(s > 0.0)) throw std::runtime_error("periodic tables: no coupling to the constrained vertex");
+  std::vector<double> lrow, invd, z0((size_t)n, 0.0), z1((size_t)n, 0.0);
+  gdm::cholesky_band(A, lrow, invd);
+  z0[0] = 1.0;
+  for (int j = 0; j < p; ++j) z1[(size_t)(n - p + j)] = r.m[(size_t)j] / s;
+  const std::vector<double> u1 = z1;
+  band_chol_solve(lrow, invd, n, p, z0.data());
+  band_chol_solve(lrow, invd, n, p, z1.data());
+  // C = S'^-1 + U'^T Z' with U' = [e_0, m / s], S' = [[c, s], [s, 0]]
+  const long double c = M(n, n), sl = s;
+  long double C[2][2] = {{0.0L, 1.0L / sl}, {1.0L / sl, -c / (sl * sl)}};
+  C[0][0] += z0[0];
+  C[0][1] += z1[0];
+  for (int k = 0; k < n; ++k) {
+    C[1][0] += (long double)u1[(size_t)k] * z0[(size_t)k];
+    C[1][1] += (long double)u1[(size_t)k] * z1[(size_t)k];
+  }
+  const long double det = C[0][0] * C[1][1] - C[0][1] * C[1][0];
+  if (det == 0.0L) throw std::runtime_error("periodic tables: singular capacitance matrix");
+  const long double I[2][2] = {{C[1][1] / det, -C[0][1] / det}, {-C[1][0] / det, C[0][0] / det}};
+  r.T.resize((size_t)n * 2);
+  std::vector<char> sig((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const long double t0 = z0[(size_t)k] * I[0][0] + z1[(size_t)k] * I[1][0];
+    const long double t1 = z0[(size_t)k] * I[0][1] + z1[(size_t)k] * I[1][1];
+    r.T[(size_t)2 * k] = (double)t0;
+    r.T[(size_t)2 * k + 1] = (double)(t1 / sl);
+    sig[(size_t)k] = std::max(std::abs(r.T[(size_t)2 * k]), std::abs(r.T[(size_t)2 * k + 1]) * s) > 1e-18;
+  }
+  int best_a = n, best_b = n;  // the skipped rows [a, b); row 0 always stays (x_{N-1} copies it)
+  for (int k = 1; k < n;) {
+    if (sig[(size_t)k]) {
+      ++k;
+      continue;
+    }
+    int e = k;
+    while (e < n && !sig[(size_t)e]) ++e;
+    if (e - k > best_b - best_a) best_a = k, best_b = e;
+    k = e;
+  }
+  r.rows_lo = best_a;
+  r.rows_hi = n - best_b;
+  return r;
+}
+
+gdm::Band mesh_mass_1d(const gdm_mesh_desc *mesh, int axis) {
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  return gdm::assemble_1d(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc).M;
+}
+
+// host-only entry points: the mesh arguments gdm_op_create would accept
+const char *host_mesh_error(const gdm_mesh_desc *mesh, int axis) {
+  if (!mesh) return "mesh is NULL";
+  const int dim = mesh->dim, p = mesh->fe_degree;
+  if (dim < 1 || dim > 3) return "dim must be 1, 2 or 3";
+  if (p < 1 || p > 9 || p % 2 == 0) return "fe_degree must be odd in [1, 9]";
+  if (axis < 0 || axis >= dim) return "axis outside [0, dim)";
+  if (mesh->n_subdivisions[axis] < p) return "n_subdivisions must be >= fe_degree";
+  if (!(mesh->hi[axis] > mesh->lo[axis])) return "empty box";
+  return nullptr;
+}
+
+void build_periodic_mass(gdm_op *op) {
+  PeriodicMass &P = op->pmass;
+  int64_t max_lines = 1;
+  const int64_t n = std::max<int64_t>(op->layout.n_owned, 1);
+  int64_t stride = 1;
+  for (int d = 0; d < op->dim; stride *= op->N[d], ++d) {
+    if (!(op->mesh.periodic & (1 << d))) continue;
+    const PeriodicTables1D t = periodic_tables_1d(mesh_mass_1d(&op->mesh, d), op->p);
+    int ax = 0;
+    while (op->kdir[ax] != d) ++ax;
+    P.tab[ax] = build_line_tables(op, t.At);
+    P.axis_tab[ax] = &P.tab[ax];
+    gdmk::PeriodicDir &D = P.dir[d];
+    D.s = stride;
+    D.N = op->N[d];
+    D.n_outer = n / (stride * D.N);
+    D.p = op->p;
+    D.rows_lo = t.rows_lo;
+    D.rows_hi = t.rows_hi;
+    D.T = keep(op, dev_upload(t.T));
+    D.m = keep(op, dev_upload(t.m));
+    max_lines = std::max(max_lines, D.s * D.n_outer);
+  }
+  P.w = keep(op, dev_upload(std::vector<double>((size_t)(2 * max_lines), 0.0)));
+  // the scratch vectors a solve or an apply would otherwise allocate at its first call
+  op->mass_tmp = keep(op, dev_upload(std::vector<double>((size_t)n, 0.0)));
+  op->mass_tmp_size = n;
+  if (!op->pscratch)
+    op->pscratch = keep(op, dev_upload(std::vector<double>((size_t)std::max<int64_t>(op->layout.n_local, 1), 0.0)));
+}
+
+// the corrections of gdm_mass_solve_periodic after the line passes, z .. x; the
+// last one in its RK form when rk is given (x_owned then holds no result)
+void periodic_corrections(gdm_op *op, double *x_owned, const gdmk::RkOut *rk) {
+  int last = 0;
+  while (!(op->mesh.periodic & (1 << last))) ++last;
+  for (int d = op->dim - 1; d >= 0; --d) {
+    if (!(op->mesh.periodic & (1 << d))) continue;
+    const gdmk::PeriodicDir &D = op->pmass.dir[d];
+    hip_check(gdmk_launch_periodic_gather(D, x_owned, op->pmass.w, op->stream), "periodic gather");
+    hip_check(gdmk_launch_periodic_apply(D, x_owned, op->pmass.w, d == last ? rk : nullptr, op->stream),
+              "periodic correction");
+  }
+}
+
 // diagonal block of M on planes [pb, pe) and its spikes:
 // V[k][j] = (A^-1 M[pb:pe, pe + j])_k, W[k][j] = (A^-1 M[pb:pe, pb - p + j])_k
 struct SlabSpikes {
@@ -1132,12 +1284,14 @@ void build_spike(gdm_op *op) {
 }
 
 // the line solves of M^-1 along every kernel axis; `part` replaces the
-// partitioned axis' tables by the slab's diagonal block (multi-rank)
+// partitioned axis' tables by the slab's diagonal block (multi-rank), a
+// non-NULL axis_tab[ax] those of kernel axis ax at the unchanged line length
+// (periodic directions: A~, gdm_mass_solve_periodic)
 // rk (single rank): the RK stage update of gdm_mass_solve_rk fused into the
 // last pass when that is the unsegmented v3 x pass; returns whether it was
 // (else x_owned holds M^-1 rhs and the caller updates)
 bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, const LineTables *part,
-                       const gdmk::RkOut *rk = nullptr) {
+                       const gdmk::RkOut *rk = nullptr, const LineTables *const *axis_tab = nullptr) {
   const int64_t n = op->layout.n_owned;
   if (n <= 0) return false;
   int64_t K[3] = {op->K[0], op->K[1], op->K[2]};
@@ -1152,6 +1306,9 @@ bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, con
     tab[ax].row_lo = op->row_lo3[ax];
     tab[ax].row_hi = op->row_hi3[ax];
   }
+  if (axis_tab)
+    for (int ax = 0; ax < 3; ++ax)
+      if (axis_tab[ax]) tab[ax] = *axis_tab[ax];
   if (part) {
     tab[op->part_axis] = *part;
     K[op->part_axis] = op->layout.owned_plane_end - op->layout.owned_plane_begin;
@@ -1323,6 +1480,7 @@ int gdm_op_create(const gdm_mesh_desc *mesh, int kind, const double *params, int
   build_layout(op);
   build_tables(op);
   build_faces(op);
+  if (mesh->periodic) build_periodic_mass(op);
   op->zchunk = choose_zchunk(op);
   hip_check(hipMalloc(&op->dot_partial, sizeof(double) * op->n_dot_partial), "hipMalloc");
   keep(op, op->dot_partial);
@@ -1866,7 +2024,7 @@ int gdm_mass_solve(gdm_op *op, const double *rhs_owned, double *x_owned) {
     return fail(GDM_ERR_UNSUPPORTED,
                 "gdm_mass_solve: single rank; multi-rank: gdm_mass_solve_slab + ghost exchange + gdm_mass_solve_interface");
   if (op->mesh.periodic)
-    return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve: periodic constraints couple the line ends; use gdm_mass_solve_cg");
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve: periodic constraints couple the line ends; use gdm_mass_solve_periodic");
   if (!rhs_owned || !x_owned) return fail(GDM_ERR_ARG, "NULL vector");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
@@ -1879,7 +2037,7 @@ int gdm_mass_solve_rk(gdm_op *op, double *rhs_owned, double beta, const double *
                       double alpha, const double *y, double *Y) {
   if (!op) return fail(GDM_ERR_ARG, "op is NULL");
   if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve_rk: single rank");
-  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve_rk: periodic constraints");
+  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve_rk: periodic constraints; use gdm_mass_solve_periodic_rk");
   if (!rhs_owned || !acc_in || !acc_out || (Y && !y)) return fail(GDM_ERR_ARG, "NULL vector");
   {
     // the fused x pass reads rhs one chunk ahead of the stores to acc_out / Y,
@@ -1902,6 +2060,74 @@ int gdm_mass_solve_rk(gdm_op *op, double *rhs_owned, double beta, const double *
     hip_check(gdmk_launch_rk_update(op->layout.n_owned, beta, rhs_owned, acc_in, acc_out, alpha, Y ? y : nullptr, Y,
                                     op->stream),
               "rk_update");
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_mass_solve_periodic(gdm_op *op, const double *rhs_owned, double *x_owned) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve_periodic: single rank");
+  if (!op->mesh.periodic) return gdm_mass_solve(op, rhs_owned, x_owned);
+  if (!rhs_owned || !x_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  mass_solve_passes(op, rhs_owned, x_owned, nullptr, nullptr, op->pmass.axis_tab);
+  periodic_corrections(op, x_owned, nullptr);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_mass_solve_periodic_rk(gdm_op *op, double *rhs_owned, double beta, const double *acc_in, double *acc_out,
+                               double alpha, const double *y, double *Y) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_mass_solve_periodic_rk: single rank");
+  if (!op->mesh.periodic) return gdm_mass_solve_rk(op, rhs_owned, beta, acc_in, acc_out, alpha, y, Y);
+  if (!rhs_owned || !acc_in || !acc_out || (Y && !y)) return fail(GDM_ERR_ARG, "NULL vector");
+  {
+    // the aliasing rules of gdm_mass_solve_rk: the fused correction reads rhs
+    // and every input element before it writes that element
+    const int64_t n = op->layout.n_owned;
+    auto overlap = [n](const double *a, const double *b) { return a && b && a < b + n && b < a + n; };
+    auto partial = [&](const double *a, const double *b) { return overlap(a, b) && a != b; };
+    if (overlap(rhs_owned, acc_in) || overlap(rhs_owned, acc_out) || overlap(rhs_owned, y) || overlap(rhs_owned, Y))
+      return fail(GDM_ERR_ARG, "gdm_mass_solve_periodic_rk: rhs_owned overlaps acc_in / acc_out / y / Y");
+    if (overlap(acc_out, Y) || partial(acc_out, acc_in) || partial(acc_out, y) || partial(Y, acc_in) ||
+        partial(Y, y))
+      return fail(GDM_ERR_ARG, "gdm_mass_solve_periodic_rk: acc_out / Y must be distinct, or equal (not partially "
+                               "overlapping) to an input");
+  }
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const gdmk::RkOut rk{acc_in, acc_out, Y ? y : nullptr, Y, beta, alpha};
+  mass_solve_passes(op, rhs_owned, rhs_owned, nullptr, nullptr, op->pmass.axis_tab);
+  periodic_corrections(op, rhs_owned, &rk);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_mass_periodic_tables(const gdm_mesh_desc *mesh, int axis, double *T_host, double *m_host, int *rows_lo,
+                             int *rows_hi) {
+  if (const char *e = host_mesh_error(mesh, axis)) return fail(GDM_ERR_ARG, e);
+  if (!T_host || !m_host || !rows_lo || !rows_hi) return fail(GDM_ERR_ARG, "NULL argument");
+  GDM_GUARD_BEGIN
+  const PeriodicTables1D t = periodic_tables_1d(mesh_mass_1d(mesh, axis), mesh->fe_degree);
+  std::copy(t.T.begin(), t.T.end(), T_host);
+  std::copy(t.m.begin(), t.m.end(), m_host);
+  *rows_lo = t.rows_lo;
+  *rows_hi = t.rows_hi;
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_mass_cholesky_1d(const gdm_mesh_desc *mesh, int axis, int periodic, double *lrow_host, double *invd_host) {
+  if (const char *e = host_mesh_error(mesh, axis)) return fail(GDM_ERR_ARG, e);
+  if (!lrow_host || !invd_host) return fail(GDM_ERR_ARG, "NULL argument");
+  GDM_GUARD_BEGIN
+  const gdm::Band M = mesh_mass_1d(mesh, axis);
+  std::vector<double> lrow, invd;
+  gdm::cholesky_band(periodic ? periodic_tables_1d(M, mesh->fe_degree).At : M, lrow, invd);
+  std::copy(lrow.begin(), lrow.end(), lrow_host);
+  std::copy(invd.begin(), invd.end(), invd_host);
   return GDM_OK;
   GDM_GUARD_END
 }

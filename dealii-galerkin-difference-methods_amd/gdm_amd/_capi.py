@@ -148,6 +148,11 @@ def load():
         "gdm_mass_apply": [P, P, P],
         "gdm_mass_solve": [P, P, P],
         "gdm_mass_solve_rk": [P, P, d, P, P, d, P, P],
+        "gdm_mass_solve_periodic": [P, P, P],
+        "gdm_mass_solve_periodic_rk": [P, P, d, P, P, d, P, P],
+        "gdm_mass_periodic_tables": [ctypes.POINTER(MeshDesc), i32, P, P, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int)],
+        "gdm_mass_cholesky_1d": [ctypes.POINTER(MeshDesc), i32, i32, P, P],
         "gdm_constraints_distribute": [P, P],
         "gdm_mass_solve_cg": [P, P, P, d, d, i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
         "gdm_mass_solve_lines": [P, i32, P, i64, i64, i64, i64, i64],
@@ -297,6 +302,38 @@ def field_tile(fe_degree):
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_field_tile(int(fe_degree), *[ctypes.byref(v) for v in t]), "gdm_field_tile")
     return tuple(v.value for v in t)
+
+
+def mass_periodic_tables(mesh, axis):
+    """Host tables of the periodic mass inverse along `axis` (pure host, no
+    GPU): (T [N-1, 2], m [p], rows_lo, rows_hi), gdm_mass_periodic_tables."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("mass_periodic_tables: axis outside [0, dim)")
+    n, p = mesh.n_subdivisions[axis], mesh.fe_degree
+    T, m = np.zeros((n, 2)), np.zeros(p)
+    lo, hi = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().gdm_mass_periodic_tables(ctypes.byref(mesh), int(axis), T.ctypes.data_as(ctypes.c_void_p),
+                                          m.ctypes.data_as(ctypes.c_void_p), ctypes.byref(lo), ctypes.byref(hi)),
+          "gdm_mass_periodic_tables")
+    return T, m, lo.value, hi.value
+
+
+def mass_cholesky_1d(mesh, axis, periodic=False):
+    """(lrow [N, p+1], invd [N]): the banded Cholesky rows of the 1D mass
+    matrix along `axis`, or (periodic) of blockdiag(M[0:N-1, 0:N-1], 1) (pure
+    host, no GPU; gdm_mass_cholesky_1d)."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("mass_cholesky_1d: axis outside [0, dim)")
+    N, p = mesh.n_subdivisions[axis] + 1, mesh.fe_degree
+    lrow, invd = np.zeros((N, p + 1)), np.zeros(N)
+    check(load().gdm_mass_cholesky_1d(ctypes.byref(mesh), int(axis), int(bool(periodic)),
+                                      lrow.ctypes.data_as(ctypes.c_void_p), invd.ctypes.data_as(ctypes.c_void_p)),
+          "gdm_mass_cholesky_1d")
+    return lrow, invd
 
 
 def mass_spike_rounds(dim, fe_degree, n_subdivisions, n_ranks, lo=0.0, hi=1.0):

@@ -213,6 +213,34 @@ class GdmOperator:
         check(self.lib.gdm_mass_solve(self.h, _ptr(rhs_owned), _ptr(x_owned)), "gdm_mass_solve")
         return x_owned
 
+    def mass_solve_periodic(self, rhs_owned, x_owned):
+        """x = distribute((P^T M P)^-1 rhs): the exact, direct mass inverse
+        with periodicity constraints (gdm_mass_solve_periodic); rhs entries on
+        constrained DoFs are ignored; x may be rhs.  Without periodic
+        constraints: mass_solve."""
+        self._check_sizes(None, rhs_owned)
+        self._check_sizes(None, x_owned)
+        check(self.lib.gdm_mass_solve_periodic(self.h, _ptr(rhs_owned), _ptr(x_owned)), "gdm_mass_solve_periodic")
+        return x_owned
+
+    def mass_solve_periodic_rk(self, rhs_owned, beta, acc_in, acc_out, alpha=0.0, y=None, Y=None):
+        """mass_solve_rk with periodicity constraints
+        (gdm_mass_solve_periodic_rk): rhs_owned is overwritten; the same bits
+        as mass_solve_periodic(rhs, rhs) + rk_update"""
+        n = self.n_owned
+        for v in (rhs_owned, acc_in, acc_out) + ((y, Y) if Y is not None else ()):
+            if v.numel() != n:
+                raise GdmError("mass_solve_periodic_rk: vectors need n_owned = %d entries" % n)
+        check(self.lib.gdm_mass_solve_periodic_rk(self.h, _ptr(rhs_owned), float(beta), _ptr(acc_in), _ptr(acc_out),
+                                                  float(alpha), _ptr(y) if Y is not None else None, _ptr(Y)),
+              "gdm_mass_solve_periodic_rk")
+        return acc_out
+
+    def mass_periodic_tables(self, axis):
+        """(T, m, rows_lo, rows_hi) of the periodic mass inverse along `axis`
+        (gdm_mass_periodic_tables, pure host)"""
+        return _capi.mass_periodic_tables(self.mesh, axis)
+
     def mass_solve_cg(self, rhs_owned, x_owned, rel_tol=1e-8, abs_tol=1e-10, max_it=100, precond=1):
         """SolverCG on the matrix-free (condensed) mass: returns (iterations, residual)"""
         self._check_sizes(None, rhs_owned)

@@ -219,11 +219,18 @@ class Advection01:
     ReductionControl(100, 1e-10, 1e-8) from a zero initial guess (:208-217),
     RK_CLASSIC_FOURTH_ORDER + DiscreteTime, constraints.distribute after
     every step (:268).  `op` is a "convective" operator with periodic = all
-    directions."""
+    directions.
 
-    def __init__(self, op):
+    mass_solver="cg" is the reference's solve.  mass_solver="direct" replaces
+    it by the exact periodic mass inverse fused with the stage update
+    (GdmOperator.mass_solve_periodic_rk): no CG, cg_iterations stays empty."""
+
+    def __init__(self, op, mass_solver="cg"):
         if op.mesh.n_ranks != 1:
             raise GdmError("Advection01: single rank")
+        if mass_solver not in ("cg", "direct"):
+            raise GdmError("Advection01: mass_solver is 'cg' or 'direct'")
+        self.mass_solver = mass_solver
         self.op = op
         self.u = op.new_vector(False)
         self._acc, self._Y, self._k = (op.new_vector(False) for _ in range(3))
@@ -246,11 +253,17 @@ class Advection01:
         op, y = self.op, self.u
         acc, Y, k = self._acc, self._Y, self._k
         stage = y
+        direct = self.mass_solver == "direct"
         for s in range(4):
-            self.rhs(stage, k)
             last = s == 3
-            op.rk_update(h * RK4_B[s], k, y if s == 0 else acc, y if last else acc,
-                         0.0 if last else h * RK4_A[s], None if last else y, None if last else Y)
+            upd = (h * RK4_B[s], y if s == 0 else acc, y if last else acc, 0.0 if last else h * RK4_A[s],
+                   None if last else y, None if last else Y)
+            if direct:
+                op.apply(stage, self._r_tmp())
+                op.mass_solve_periodic_rk(self._r, *upd)
+            else:
+                self.rhs(stage, k)
+                op.rk_update(upd[0], k, *upd[1:])
             stage = Y
         op.distribute(y)
 

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GDM_HIP_ABI_VERSION 16
+#define GDM_HIP_ABI_VERSION 17
 
 enum gdm_status {
   GDM_OK = 0,
@@ -262,7 +262,7 @@ int gdm_op_set_field_scale(gdm_op *op, const double *s);
 /* dst_owned = M src_local */
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned);
 /* x_owned = M^-1 rhs_owned (exact Kronecker inverse; single rank; not with
- * periodic constraints: gdm_mass_solve_cg) */
+ * periodic constraints: gdm_mass_solve_periodic) */
 int gdm_mass_solve(gdm_op *op, const double *rhs_owned, double *x_owned);
 /* gdm_mass_solve_rk: k = M^-1 rhs, then gdm_vec_rk_update's acc_out = acc_in +
  * beta k and, when Y != NULL, Y = y + alpha k -- one RK stage's solve and
@@ -272,9 +272,46 @@ int gdm_mass_solve(gdm_op *op, const double *rhs_owned, double *x_owned);
  * none of acc_in / acc_out / y / Y; acc_out and Y are distinct; a written
  * vector (acc_out, Y) may equal a read one (acc_in, y) but not partially
  * overlap it.  Same bits as gdm_mass_solve(rhs, rhs) + gdm_vec_rk_update.
- * Single rank, non-periodic. */
+ * Single rank, non-periodic (periodic: gdm_mass_solve_periodic_rk). */
 int gdm_mass_solve_rk(gdm_op *op, double *rhs_owned, double beta, const double *acc_in, double *acc_out,
                       double alpha, const double *y, double *Y);
+
+/* Exact mass inverse with periodicity constraints (ABI 17; replaces the
+ * SolverCG + PreconditionJacobi of prototypes/advection_01_gdm.cc:208-217 by a
+ * direct solve): x_owned = distribute((P^T M P)^-1 rhs_owned), the condensed
+ * mass of System::make_periodicity_constraints (system.h:427-463).  Along a
+ * periodic direction the condensed 1D matrix on the N - 1 free vertices is
+ *   M_per = A + U S U^T,  A = M[0:N-1, 0:N-1],  U = [e_0, m],  m = M[0:N-1, N-1],
+ *   S = [[M[N-1,N-1], 1], [1, 0]],
+ * and M_per^-1 b = g - T (U^T g) with g = A^-1 b, T = Z (S^-1 + U^T Z)^-1,
+ * Z = A^-1 U (Woodbury, nothing truncated).  The line passes of gdm_mass_solve
+ * run with the tables of blockdiag(A, 1) in the periodic directions; one
+ * rank-2 correction per periodic direction follows and writes x[N-1] = x[0]
+ * (bit for bit).  The rhs entries on constrained DoFs are ignored (any finite
+ * value; a condensed rhs has them zero).  x_owned may equal rhs_owned.
+ * Without periodic constraints: gdm_mass_solve, same bits.  Single rank. */
+int gdm_mass_solve_periodic(gdm_op *op, const double *rhs_owned, double *x_owned);
+/* gdm_mass_solve_rk with periodicity constraints (ABI 17; one RK stage of
+ * advection_01_gdm.cc:208-217 + :252-268 without the SolverCG): the last
+ * correction writes acc_out = acc_in + beta k and, when Y != NULL, Y = y +
+ * alpha k instead of k.  rhs_owned is overwritten (scratch).  Aliasing rules
+ * of gdm_mass_solve_rk.  Same bits as gdm_mass_solve_periodic(rhs, rhs) +
+ * gdm_vec_rk_update; without periodic constraints gdm_mass_solve_rk. */
+int gdm_mass_solve_periodic_rk(gdm_op *op, double *rhs_owned, double beta, const double *acc_in, double *acc_out,
+                               double alpha, const double *y, double *Y);
+/* The host tables of gdm_mass_solve_periodic along `axis` (pure host, no
+ * device; the direct replacement of the SolverCG of advection_01_gdm.cc:
+ * 208-217): T_host [N-1][2], m_host [p] = M[N-1-p+j, N-1], and the rows the
+ * correction touches, [0, rows_lo) and [N-1-rows_hi, N-1): a row k is skipped
+ * only if max(|T[k][0]|, |T[k][1]| max|m|) <= 1e-18.  N = n_subdivisions + 1. */
+int gdm_mass_periodic_tables(const gdm_mesh_desc *mesh, int axis, double *T_host, double *m_host, int *rows_lo,
+                             int *rows_hi);
+/* Row-form banded Cholesky factor of the 1D mass matrix along `axis` (pure
+ * host): lrow_host [N][p+1], lrow[i][k] = L(i, i - p + k); invd_host [N] =
+ * 1 / L(i, i).  periodic != 0: of blockdiag(M[0:N-1, 0:N-1], 1), the matrix the
+ * line passes of gdm_mass_solve_periodic factor -- its rows equal M's except
+ * the last one (0, ..., 0, 1). */
+int gdm_mass_cholesky_1d(const gdm_mesh_desc *mesh, int axis, int periodic, double *lrow_host, double *invd_host);
 
 /* Distributed exact mass inverse (n_ranks > 1; replaces the CG + ILU/AMG
  * solve of advection/problem.h:236-267 / wave/problem.h:457-502 across MPI
