@@ -18,6 +18,7 @@
 #include "../../include/gdm_hip.h"
 #include "gdm_coeffs.h"
 #include "gdm_kernels.h"
+#include "gdm_load.h"
 #include "gdm_periodic.h"
 #include "gdm_post.h"
 #include "gdm_rk.h"
@@ -202,7 +203,12 @@ struct gdm_op {
     std::vector<std::vector<double>> face_end;
     std::vector<void *> allocations;
   } field;
-  bool cut_inner = false;  // the inner operator of a gdm_cut_advection handle
+  bool cut_inner = false;  // the inner operator of a cut handle
+  // load vector / Dirichlet data (gdm_add_load*, gdm_add_dirichlet_data; single
+  // rank, non-periodic): shape values times quadrature weights per category,
+  // the per-axis (sin, cos) load vectors of the rank-1 path [3][2][load_ld]
+  double *load_Sw = nullptr, *load_bvec = nullptr;
+  int load_ld = 0;
 };
 
 namespace {
@@ -936,6 +942,20 @@ void apply_with_faces(gdm_op *op, bool mass, const double *src_local, double *ds
   hip_check(launch_stencil(op, mass, src_local, dst_owned), "stencil launch");
 }
 
+// tables and scratch of the load vector (gdm_add_load_fn / gdm_add_load)
+void build_load(gdm_op *op) {
+  const int p = op->p, n1 = p + 1, ncat = std::max(1, p);
+  std::vector<double> xq, wq;
+  gdm::gauss_unit(n1, xq, wq);
+  std::vector<double> Sw((size_t)ncat * n1 * n1);
+  for (int c = 0; c < ncat; ++c)
+    for (int i = 0; i < n1; ++i)
+      for (int q = 0; q < n1; ++q) Sw[((size_t)c * n1 + i) * n1 + q] = gdm::shape_1d(p, c, i, xq[q], 0) * wq[q];
+  op->load_Sw = keep(op, dev_upload(Sw));
+  op->load_ld = std::max({op->K[0], op->K[1], op->K[2]});
+  op->load_bvec = keep(op, dev_upload(std::vector<double>((size_t)6 * op->load_ld, 0.0)));
+}
+
 int choose_zchunk(const gdm_op *op) {
   const int nz = op->part_axis == 2 ? (op->layout.owned_plane_end - op->layout.owned_plane_begin) : 1;
   const int ty = gdmk_stencil_tile_rows(op->p);
@@ -1481,6 +1501,7 @@ int gdm_op_create(const gdm_mesh_desc *mesh, int kind, const double *params, int
   build_tables(op);
   build_faces(op);
   if (mesh->periodic) build_periodic_mass(op);
+  if (mesh->n_ranks == 1 && !mesh->periodic) build_load(op);
   op->zchunk = choose_zchunk(op);
   hip_check(hipMalloc(&op->dot_partial, sizeof(double) * op->n_dot_partial), "hipMalloc");
   keep(op, op->dot_partial);
@@ -2624,6 +2645,150 @@ int gdm_error_norms(gdm_op *op, const double *u_local, int fn_kind, const double
   GDM_GUARD_END
 }
 
+}  // extern "C"
+
+namespace {
+
+// shared checks of the data-term entry points; 0 = ok
+int check_load_op(gdm_op *op, const char *what) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->mesh.n_ranks > 1) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": single rank only");
+  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": not with periodic constraints");
+  if (op->cut_inner) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": not on the inner operator of a cut handle");
+  if (!op->load_Sw) return fail(GDM_ERR_STATE, std::string(what) + ": load tables missing");
+  return GDM_OK;
+}
+
+// the mesh in kernel axes
+gdmk::LoadGeom load_geom(const gdm_op *op) {
+  gdmk::LoadGeom g{};
+  g.p = op->p;
+  g.jxw = 1.0;
+  for (int ax = 0; ax < 3; ++ax) {
+    const int d = op->kdir[ax];
+    g.rdir[ax] = d;
+    g.on[ax] = d >= 0;
+    g.K[ax] = d >= 0 ? op->N[d] : 1;
+    g.nc[ax] = d >= 0 ? op->mesh.n_subdivisions[d] : 1;
+    g.Q[ax] = d >= 0 ? g.nc[ax] * (op->p + 1) : 1;
+    g.lo[ax] = d >= 0 ? op->mesh.lo[d] : 0.0;
+    g.h[ax] = d >= 0 ? (op->mesh.hi[d] - op->mesh.lo[d]) / op->mesh.n_subdivisions[d] : 1.0;
+    if (d >= 0) g.jxw *= g.h[ax];
+  }
+  for (int q = 0; q <= op->p; ++q) g.xq[q] = op->xq[q];
+  return g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gdm_add_load_fn(gdm_op *op, int fn_kind, const double *params, int n_params, double t, int derivative,
+                    double scale, double *dst_owned) {
+  if (int rc = check_load_op(op, "gdm_add_load_fn")) return rc;
+  if (op->layout.n_owned > 0 && !dst_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  if (derivative != 0 && derivative != 1) return fail(GDM_ERR_ARG, "derivative must be 0 or 1");
+  if (int rc = check_bc_fn(op, fn_kind, params, n_params)) return rc;
+  // d/dt of the constant and of the cone is zero (gdm_eval_boundary)
+  if (scale == 0.0 || (derivative && fn_kind != GDM_FN_SINE_PRODUCT)) return GDM_OK;
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const gdmk::LoadGeom g = load_geom(op);
+  gdmk::BcFn fn{};
+  fn.kind = fn_kind;
+  fn.dim = op->dim;
+  for (int i = 0; i < n_params && i < 12; ++i) fn.prm[i] = params[i];
+  if (fn_kind == GDM_FN_CONE)
+    hip_check(gdmk_launch_load(g, fn, 1, op->load_Sw, nullptr, scale, dst_owned, op->stream), "load (cone)");
+  else
+    hip_check(gdmk_launch_load_rank1(g, fn, t, derivative, scale, op->load_Sw, op->load_bvec, op->load_ld, dst_owned,
+                                     op->stream),
+              "load (rank 1)");
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_add_load(gdm_op *op, const double *fq, double scale, double *dst_owned) {
+  if (int rc = check_load_op(op, "gdm_add_load")) return rc;
+  if (!fq || (op->layout.n_owned > 0 && !dst_owned)) return fail(GDM_ERR_ARG, "NULL vector");
+  if (scale == 0.0) return GDM_OK;
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const gdmk::LoadGeom g = load_geom(op);
+  hip_check(gdmk_launch_load(g, gdmk::BcFn{}, 0, op->load_Sw, fq, scale, dst_owned, op->stream), "load");
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_add_dirichlet_data(gdm_op *op, const double *g_bc, double *dst_owned) {
+  if (int rc = check_load_op(op, "gdm_add_dirichlet_data")) return rc;
+  if (op->kind != GDM_OP_WAVE || !(op->nitsche > 0.0))
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_add_dirichlet_data: wave operators created with nitsche > 0 only");
+  if (!g_bc || !dst_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const int p = op->p;
+  double hmin = 1e300, h[3] = {1.0, 1.0, 1.0};
+  for (int d = 0; d < op->dim; ++d) {
+    h[d] = (op->mesh.hi[d] - op->mesh.lo[d]) / op->mesh.n_subdivisions[d];
+    hmin = std::min(hmin, h[d]);
+  }
+  const int64_t stride[3] = {1, op->N[0], (int64_t)op->N[0] * op->N[1]};
+  // one launch per face, stream-ordered: the faces share the (p+1)-deep edge and corner columns
+  for (const Face &F : op->faces) {
+    gdmk::DirFace A{};
+    A.n0 = F.t0.n_nodes;
+    A.n1 = F.t1.n_nodes;
+    A.Q0 = F.t0.Q;
+    A.Q1 = F.t1.Q;
+    if ((int64_t)A.Q1 * A.n0 > op->face_tmp_size) return fail(GDM_ERR_STATE, "gdm_add_dirichlet_data: face scratch");
+    A.wmax0 = F.t0.wmax;
+    A.wmax1 = F.t1.wmax;
+    A.qs0 = F.t0.qs;
+    A.qc0 = F.t0.qc;
+    A.qs1 = F.t1.qs;
+    A.qc1 = F.t1.qc;
+    A.w0 = F.t0.w;
+    A.w1 = F.t1.w;
+    A.stride0 = F.t0.stride;
+    A.stride1 = F.t1.stride;
+    A.goff = F.offset;
+    A.stride_d = stride[F.d];
+    A.base = (F.side ? (int64_t)(op->N[F.d] - 1 - p) : 0) * stride[F.d];
+    A.nk = p + 1;
+    const int cat = F.side ? (int)gdm::category((unsigned)op->mesh.n_subdivisions[F.d] - 1, (unsigned)p,
+                                                (unsigned)op->mesh.n_subdivisions[F.d])
+                           : 0;
+    const double xs = F.side ? 1.0 : 0.0, nrm = F.side ? 1.0 : -1.0;
+    for (int k = 0; k <= p; ++k)
+      A.ck[k] = op->nitsche / hmin * gdm::shape_1d(p, cat, k, xs, 0) - nrm * gdm::shape_1d(p, cat, k, xs, 1) / h[F.d];
+    hip_check(gdmk_launch_dirichlet_face(A, g_bc, op->face_tmp, dst_owned, op->stream), "dirichlet data");
+  }
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_load_vector_1d(const gdm_mesh_desc *mesh, int axis, const double *f, double *b_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  if (!b_host) return fail(GDM_ERR_ARG, "b_host is NULL");
+  GDM_GUARD_BEGIN
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  const double h = (mesh->hi[axis] - mesh->lo[axis]) / nc;
+  const std::vector<double> b = gdm::load_vector_1d(mesh->fe_degree, nc, h, f ? f + 1 : nullptr);
+  std::copy(b.begin(), b.end(), b_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_load_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (tile_x) *tile_x = gdmk::LOAD_TX;
+  if (tile_y) *tile_y = gdmk::LOAD_TY;
+  if (z_chunk) *z_chunk = gdmk::LOAD_ZC;
+  return GDM_OK;
+}
+
 int gdm_vec_dot(gdm_op *op, int64_t n, const double *x, const double *y, double *result_host) {
   if (!op || !result_host || (n > 0 && (!x || !y))) return fail(GDM_ERR_ARG, "NULL argument");
   GDM_GUARD_BEGIN
@@ -3230,6 +3395,7 @@ int gdm_cut_wave_create(int dim, int fe_degree, int n_subdivisions, double left,
       delete c;
       return rc;
     }
+    c->op->cut_inner = true;  // the data terms of the cut system are Ff, Fg, not the box's
     gdmh_cut_wave_info(c->host, &c->n_dofs, &c->n_quad, &c->n_surf, c->cells);
     gdm_layout L{};
     if (gdm_op_layout(c->op, &L) != GDM_OK || L.n_local != c->n_dofs || L.n_owned != c->n_dofs)

@@ -161,6 +161,28 @@ WeightedMatrices1D assemble_1d_weighted(int p, unsigned n_cells, double h, const
   return m;
 }
 
+std::vector<double> load_vector_1d(int p, unsigned n_cells, double h, const double *f) {
+  if (n_cells < (unsigned)p) throw std::invalid_argument("n_subdivisions must be >= fe_degree");
+  const int n1 = p + 1;
+  std::vector<double> xq, wq, b((size_t)n_cells + 1, 0.0);
+  gauss_unit(n1, xq, wq);
+  const int ncat = std::max(1, p);
+  std::vector<double> val((size_t)ncat * n1 * n1);
+  for (int cat = 0; cat < ncat; ++cat)
+    for (int i = 0; i < n1; ++i)
+      for (int q = 0; q < n1; ++q) val[((size_t)cat * n1 + i) * n1 + q] = shape_1d(p, cat, i, xq[q], 0) * wq[q];
+  for (unsigned c = 0; c < n_cells; ++c) {
+    const double *v = &val[(size_t)category(c, p, n_cells) * n1 * n1];
+    const int off = int(box_offset(c, p, n_cells));
+    for (int i = 0; i < n1; ++i) {
+      double s = 0.0;
+      for (int q = 0; q < n1; ++q) s += v[i * n1 + q] * (f ? f[(size_t)c * n1 + q] : 1.0);
+      b[off + i] += s * h;
+    }
+  }
+  return b;
+}
+
 std::vector<double> field_points_1d(int p, unsigned n_cells, double lo, double hi) {
   const int n1 = p + 1;
   std::vector<double> xq, wq, x;

@@ -163,6 +163,12 @@ def load():
         "gdm_apply_bc_fn": [P, P, P, i32, P, i32, d, d, d],
         "gdm_add_boundary_fn": [P, P, i32, P, i32, d, d, d],
         "gdm_error_norms": [P, P, i32, P, i32, d, P, P],
+        "gdm_add_load_fn": [P, i32, P, i32, d, i32, d, P],
+        "gdm_add_load": [P, P, d, P],
+        "gdm_add_dirichlet_data": [P, P, P],
+        "gdm_load_vector_1d": [ctypes.POINTER(MeshDesc), i32, P, P],
+        "gdm_load_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                          ctypes.POINTER(ctypes.c_int)],
         "gdm_mass_spike_eps": [P, P],
         "gdm_mass_solve_slab": [P, P, P],
         "gdm_mass_solve_interface": [P, P],
@@ -301,6 +307,35 @@ def field_tile(fe_degree):
     """(tile_x, tile_y, z_chunk) of the separable field's volume kernel, kernel axes"""
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_field_tile(int(fe_degree), *[ctypes.byref(v) for v in t]), "gdm_field_tile")
+    return tuple(v.value for v in t)
+
+
+def load_vector_1d(mesh, axis, f=None):
+    """The 1D load vector b[i] = sum_q w_q h phi_i(x_q) f(x_q) along `axis`
+    (n_sub + 1 entries); f sampled at field_points (None: f = 1; the two end
+    values are not read).  Pure host, no GPU (gdm_load_vector_1d)."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("load_vector_1d: axis outside [0, dim)")
+    n = mesh.n_subdivisions[axis]
+    fp = None
+    if f is not None:
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.size != n * (mesh.fe_degree + 1) + 2:
+            raise GdmError("load_vector_1d: f has %d samples, field_points has %d"
+                           % (f.size, n * (mesh.fe_degree + 1) + 2))
+        fp = f.ctypes.data_as(ctypes.c_void_p)
+    b = np.zeros(n + 1)
+    check(load().gdm_load_vector_1d(ctypes.byref(mesh), int(axis), fp, b.ctypes.data_as(ctypes.c_void_p)),
+          "gdm_load_vector_1d")
+    return b
+
+
+def load_tile(fe_degree, dim=3):
+    """(tile_x, tile_y, z_chunk) of the general load kernel, kernel axes (gdm_load_tile)"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_load_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_load_tile")
     return tuple(v.value for v in t)
 
 

@@ -305,6 +305,50 @@ class GdmOperator:
                                            float(alpha), float(t_k)), "gdm_add_boundary_fn")
         return dst_owned
 
+    # -- forcing and Dirichlet data (wave / heat right-hand side) ----------------
+    def quadrature_points(self):
+        """Per-axis Gauss abscissae of the tensor quadrature grid of add_load:
+        entries 1 .. Q_d of field_points(d), Q_d = n_sub_d (p + 1)."""
+        return [_capi.field_points(self.mesh, d)[1:-1] for d in range(self.dim)]
+
+    def add_load_fn(self, fn_kind, params, t, dst_owned, derivative=0, scale=1.0):
+        """dst += scale (v, f) over QGauss(p+1), f a built-in function at time
+        t or (derivative=1) its d/dt (gdm_add_load_fn; wave/stiffness.h:196-200)"""
+        self._check_sizes(None, dst_owned)
+        prm = (ctypes.c_double * max(len(params), 1))(*[float(v) for v in params])
+        check(self.lib.gdm_add_load_fn(self.h, int(fn_kind), prm, len(params), float(t), int(derivative),
+                                       float(scale), _ptr(dst_owned)), "gdm_add_load_fn")
+        return dst_owned
+
+    def add_load(self, fq, dst_owned, scale=1.0):
+        """dst += scale (v, f), f a device array on the tensor Gauss grid
+        fq[(qz Q_y + qy) Q_x + qx] (quadrature_points(); gdm_add_load)"""
+        self._check_sizes(None, dst_owned)
+        nq = 1
+        for d in range(self.dim):
+            nq *= self.mesh.n_subdivisions[d] * (self.p + 1)
+        if fq.numel() != nq:
+            raise GdmError("add_load: fq has %d entries, the quadrature grid %d" % (fq.numel(), nq))
+        check(self.lib.gdm_add_load(self.h, _ptr(fq), float(scale), _ptr(dst_owned)), "gdm_add_load")
+        return dst_owned
+
+    def add_dirichlet_data(self, g_bc, dst_owned):
+        """dst += sum_faces <gamma / h_min v - dv/dn, g>, g in the device
+        block(0) order (gdm_add_dirichlet_data; wave/stiffness.h:320-326)"""
+        self._check_sizes(None, dst_owned)
+        if g_bc.numel() != self.n_bc_points:
+            raise GdmError("add_dirichlet_data: g has %d entries, expected %d" % (g_bc.numel(), self.n_bc_points))
+        check(self.lib.gdm_add_dirichlet_data(self.h, _ptr(g_bc), _ptr(dst_owned)), "gdm_add_dirichlet_data")
+        return dst_owned
+
+    def load_vector_1d(self, axis, f=None):
+        """1D load vector along `axis` (gdm_load_vector_1d, pure host)"""
+        return _capi.load_vector_1d(self.mesh, axis, f)
+
+    def load_tile(self):
+        """(tile_x, tile_y, z_chunk) of the general load kernel, kernel axes"""
+        return _capi.load_tile(self.p, self.dim)
+
     def mass_solve_slab(self, rhs_owned, x_owned):
         """Distributed exact mass inverse, step 1: the slab-local solve
         (gdm_mass_solve_slab).  Then exchange the ghost planes of the local

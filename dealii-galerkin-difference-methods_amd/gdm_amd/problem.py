@@ -60,10 +60,20 @@ class DiscreteTime:
         self.step += 1
 
 class WaveProblem:
-    """wave-rk on one rank: du/dt = v, dv/dt = M^-1 (K u) with K the wave
-    operator of `op` (kind "wave": -(grad v, grad u) [+ box Nitsche])."""
+    """wave-rk on one rank: du/dt = v, dv/dt = M^-1 (K u + (v, f(t)) + Nitsche
+    data of g_D(t)) with K the wave operator of `op` (kind "wave": -(grad v,
+    grad u) [+ box Nitsche]) -- compute_rhs(dst, src, true, time),
+    wave/stiffness.h:409-420.
 
-    def __init__(self, op):
+    forcing: None, (fn_kind, params, scale) for scale * a built-in function
+    (GdmOperator.add_load_fn), or a callable t -> device array on the
+    quadrature grid (add_load).  dirichlet: None, (fn_kind, params) for a
+    built-in g_D (eval_boundary), or a callable t -> device array of
+    n_bc_points values in device order (add_dirichlet_data; needs an operator
+    with nitsche > 0).  Both are taken at the stage times t + c_s h.  With both
+    None the launches are those of the homogeneous problem."""
+
+    def __init__(self, op, forcing=None, dirichlet=None):
         if op.mesh.n_ranks != 1:
             raise GdmError("WaveProblem: single-rank driver (multi-rank: gdm_amd.distributed)")
         self.op = op
@@ -73,10 +83,36 @@ class WaveProblem:
         self._Y = [op.new_vector(False) for _ in range(2)]
         self._kv = op.new_vector(False)
         self.n = n
+        self.forcing, self.dirichlet = forcing, dirichlet
+        self._g = None
+        if dirichlet is not None and not callable(dirichlet):
+            import torch
+
+            self._g = torch.zeros(max(op.n_bc_points, 1), dtype=torch.float64, device="cuda:%d" % op.device)
+            self._g = self._g[:op.n_bc_points]
+
+    def add_data(self, t, out):
+        """out += (v, f(t)) + the Nitsche data of g_D(t) (stiffness.h:196-200, 320-326)"""
+        op = self.op
+        if self.forcing is not None:
+            if callable(self.forcing):
+                op.add_load(self.forcing(t), out)
+            else:
+                fn, prm, scale = self.forcing
+                op.add_load_fn(fn, prm, t, out, 0, scale)
+        if self.dirichlet is not None:
+            if callable(self.dirichlet):
+                op.add_dirichlet_data(self.dirichlet(t), out)
+            else:
+                fn, prm = self.dirichlet
+                op.eval_boundary(fn, prm, t, 0, self._g)
+                op.add_dirichlet_data(self._g, out)
+        return out
 
     def rhs(self, t, U, out):
-        """dv/dt = M^-1 compute_rhs(U) (wave/problem.h:313-317)"""
+        """dv/dt = M^-1 compute_rhs(U, t) (wave/problem.h:313-317)"""
         self.op.apply(U, out)
+        self.add_data(t, out)
         self.op.mass_solve(out, out)
         return out
 
@@ -84,9 +120,12 @@ class WaveProblem:
         op, y = self.op, (self.u, self.v)
         acc, Y, kv = self._acc, self._Y, self._kv
         stage = y
+        data = self.forcing is not None or self.dirichlet is not None
         for s in range(4):
-            # k = (stage_v, M^-1 K stage_u)
+            # k = (stage_v, M^-1 (K stage_u + data(t + c_s h)))
             op.apply(stage[0], kv)
+            if data:
+                self.add_data(t + RK4_C[s] * h, kv)
             ku = stage[1]
             last = s == 3
             acc_in = y if s == 0 else acc

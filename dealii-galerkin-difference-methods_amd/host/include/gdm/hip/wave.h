@@ -10,8 +10,14 @@
 //   WaveProblem<dim>             .../wave/problem.h:22-346, "wave-rk" branch :280-346
 // The level set contains the box (no cut cells): the volume term
 // -(grad v, grad u), and with function_domain_dbc the box Nitsche terms
-// (gamma_D / h, :261-330); the right-hand-side function and the Dirichlet
-// data are zero (the uncut C4 configuration of BASELINE.json).
+// (gamma_D / h, :261-330).  Parameters::function_rhs and function_domain_dbc
+// bind the source term (v, f(., t)) (:196-200) and the Nitsche Dirichlet data
+// <gamma_D / h v - dv/dn, g_D(., t)> (:320-326): compute_rhs evaluates them on
+// the host at the quadrature / boundary points of the stage time, uploads the
+// values and adds both terms on the device (gdm_add_load,
+// gdm_add_dirichlet_data).  Left empty they are zero and the launches are
+// those of the homogeneous problem (the uncut C4 configuration of
+// BASELINE.json).
 #pragma once
 
 #include <gdm/hip/operators.h>
@@ -26,8 +32,10 @@ struct Parameters {
   unsigned int n_subdivisions_1D = 40;
   double geometry_left = -1.21;
   double geometry_right = 1.21;
-  double nitsche_parameter = 0.0;  // > 0: box Nitsche (function_domain_dbc with g = 0)
+  double nitsche_parameter = 0.0;  // > 0: box Nitsche (function_domain_dbc; g = 0 when it is empty)
   Function exact_solution;         // initial condition u(x, 0)
+  Function function_rhs;           // f(x, t) of the source term (v, f) (empty: 0)
+  Function function_domain_dbc;    // g_D(x, t) on the box (needs nitsche_parameter > 0; empty: 0)
   double start_t = 0.0;
   double end_t = 2.0;
   double cfl = 0.3;
@@ -68,30 +76,67 @@ class StiffnessMatrixOperator {
  public:
   explicit StiffnessMatrixOperator(const Discretization<dim> &discretization) : discretization(discretization) {}
   StiffnessMatrixOperator(const StiffnessMatrixOperator &) = delete;
-  ~StiffnessMatrixOperator() { gdm_op_destroy(op); }
+  ~StiffnessMatrixOperator() { release(); }
 
   void reinit(const Parameters<dim> &params) {
-    gdm_op_destroy(op);
-    op = nullptr;
+    release();
     const double nitsche = params.nitsche_parameter;
     check(gdm_op_create(&discretization.get_mesh(), GDM_OP_WAVE, nitsche > 0 ? &nitsche : nullptr,
                         nitsche > 0 ? 1 : 0, discretization.get_device(), &op),
           "gdm_op_create");
     check(gdm_op_layout(op, &layout), "gdm_op_layout");
     check(gdm_op_set_stream(op, nullptr), "gdm_op_set_stream");
+    function_rhs = params.function_rhs;
+    function_domain_dbc = params.function_domain_dbc;
+    const gdm_mesh_desc &m = discretization.get_mesh();
+    if (function_rhs) {  // the tensor Gauss grid of gdm_add_load
+      std::size_t nq = 1;
+      for (int d = 0; d < dim; ++d) {
+        std::vector<double> x((std::size_t)m.n_subdivisions[d] * (m.fe_degree + 1) + 2);
+        check(gdm_field_points(&m, d, x.data()), "gdm_field_points");
+        xq[d].assign(x.begin() + 1, x.end() - 1);
+        nq *= xq[d].size();
+      }
+      fq_host.assign(nq, 0.0);
+      fq_dev = device_buffer(nq);
+    }
+    if (function_domain_dbc) {
+      if (!(nitsche > 0)) throw Error("function_domain_dbc needs nitsche_parameter > 0");
+      bc_xyz.assign((std::size_t)std::max<int64_t>(layout.n_bc_points, 1) * 3, 0.0);
+      check(gdm_bc_points(op, bc_xyz.data()), "gdm_bc_points");
+      g_host.assign((std::size_t)layout.n_bc_points, 0.0);
+      g_dev = device_buffer(g_host.size());
+    }
   }
 
   void initialize_dof_vector(VectorType &vec) const { vec.reinit(op, layout.n_local); }
 
   // vec_rhs (owned entries) = -(grad v, grad u) [+ box Nitsche] if
-  // compute_impl_part; the right-hand-side and Dirichlet-data terms vanish
-  // (f = 0, g = 0), so the explicit part is zero (stiffness.h:409-420)
+  // compute_impl_part, + (v, f(., time)) + the Nitsche data of g_D(., time)
+  // (stiffness.h:409-420; both data terms are part of the explicit part)
   void compute_rhs(VectorType &vec_rhs, const VectorType &solution, const bool compute_impl_part,
-                   const double /*time*/) const {
+                   const double time) const {
     if (compute_impl_part)
       check(gdm_apply(op, solution.get_values(), owned(vec_rhs), nullptr), "gdm_apply");
     else
       check(gdm_vec_axpby(op, layout.n_owned, 0.0, owned(vec_rhs), 0.0, owned(vec_rhs)), "gdm_vec_axpby");
+    if (function_rhs) {
+      const std::size_t Q0 = xq[0].size(), Q1 = dim > 1 ? xq[1].size() : 1, Q2 = dim > 2 ? xq[2].size() : 1;
+      for (std::size_t k = 0; k < Q2; ++k)
+        for (std::size_t j = 0; j < Q1; ++j)
+          for (std::size_t i = 0; i < Q0; ++i) {
+            const Point x{xq[0][i], dim > 1 ? xq[1][j] : 0.0, dim > 2 ? xq[2][k] : 0.0};
+            fq_host[(k * Q1 + j) * Q0 + i] = function_rhs(x, time);
+          }
+      check(gdm_memcpy_h2d(op, fq_dev, fq_host.data(), sizeof(double) * fq_host.size()), "gdm_memcpy_h2d");
+      check(gdm_add_load(op, fq_dev, 1.0, owned(vec_rhs)), "gdm_add_load");
+    }
+    if (function_domain_dbc && !g_host.empty()) {
+      for (std::size_t i = 0; i < g_host.size(); ++i)
+        g_host[i] = function_domain_dbc(Point{bc_xyz[3 * i], bc_xyz[3 * i + 1], bc_xyz[3 * i + 2]}, time);
+      check(gdm_memcpy_h2d(op, g_dev, g_host.data(), sizeof(double) * g_host.size()), "gdm_memcpy_h2d");
+      check(gdm_add_dirichlet_data(op, g_dev, owned(vec_rhs)), "gdm_add_dirichlet_data");
+    }
   }
 
   gdm_op *handle() const { return op; }
@@ -102,9 +147,27 @@ class StiffnessMatrixOperator {
   }
 
  private:
+  double *device_buffer(std::size_t n) const {
+    void *p = nullptr;
+    check(gdm_malloc(op, sizeof(double) * std::max<std::size_t>(n, 1), &p), "gdm_malloc");
+    return static_cast<double *>(p);
+  }
+  void release() {
+    if (op && fq_dev) gdm_free(op, fq_dev);
+    if (op && g_dev) gdm_free(op, g_dev);
+    fq_dev = g_dev = nullptr;
+    gdm_op_destroy(op);
+    op = nullptr;
+  }
+
   const Discretization<dim> &discretization;
   gdm_op *op = nullptr;
   gdm_layout layout{};
+  // data terms: the functions, their evaluation points and the staging buffers
+  Function function_rhs, function_domain_dbc;
+  std::vector<double> xq[3], bc_xyz;
+  mutable std::vector<double> fq_host, g_host;
+  double *fq_dev = nullptr, *g_dev = nullptr;
 };
 
 template <int dim>

@@ -2,12 +2,15 @@
 // the C++ mirror of the reference's wave operator surface (gdm/hip/wave.h), in
 // the shape of applications/wave/wave-app.cc:222-285 + problem.h:280-346.
 //
-//   wave_app DIM P N STEPS CFL OUT [NITSCHE] [DEVICE]
+//   wave_app DIM P N STEPS CFL OUT [NITSCHE] [DEVICE] [DATA]
 //
 // Box [-1.21, 1.21]^dim, initial displacement u0 = prod_d cos(0.75 pi x_d /
 // 1.21 + 0.2 d), v0 = 0, natural boundary (NITSCHE = 0) or box Nitsche with
-// gamma_D = NITSCHE.  Writes u then v after STEPS RK4 steps to OUT (raw
-// little-endian doubles, reference global order).
+// gamma_D = NITSCHE.  DATA = 1 (needs NITSCHE > 0) drives the problem with
+// function_rhs = 3 w and function_domain_dbc = w, w(x, t) = prod_d sin(2 pi
+// k_d (x_d - a_d t) + phi_d), a = (0.8, 0, 0), k = (0.4, 0.3, 0.35), phi =
+// (0.3, 0.5, 0.2), and starts from u0 = w(., 0).  Writes u then v after STEPS
+// RK4 steps to OUT (raw little-endian doubles, reference global order).
 #include <gdm/hip/wave.h>
 
 #include <cstdio>
@@ -19,7 +22,15 @@ namespace {
 const double kPi = 3.14159265358979323846;
 
 template <int dim>
-int run(int p, int n, int steps, double cfl, const char *out, double nitsche, int device) {
+double sine_product(const GDM::HIP::Point &x, double t) {
+  const double a[3] = {0.8, 0.0, 0.0}, k[3] = {0.4, 0.3, 0.35}, phi[3] = {0.3, 0.5, 0.2};
+  double v = 1.0;
+  for (int d = 0; d < dim; ++d) v *= std::sin(2.0 * kPi * k[d] * (x[d] - a[d] * t) + phi[d]);
+  return v;
+}
+
+template <int dim>
+int run(int p, int n, int steps, double cfl, const char *out, double nitsche, int device, int data) {
   GDM::HIP::Wave::Parameters<dim> params;
   params.fe_degree = p;
   params.n_subdivisions_1D = n;
@@ -29,6 +40,11 @@ int run(int p, int n, int steps, double cfl, const char *out, double nitsche, in
     for (int d = 0; d < dim; ++d) v *= std::cos(0.75 * kPi * x[d] / 1.21 + 0.2 * d);
     return v;
   };
+  if (data) {
+    params.exact_solution = sine_product<dim>;
+    params.function_rhs = [](const GDM::HIP::Point &x, double t) { return 3.0 * sine_product<dim>(x, t); };
+    params.function_domain_dbc = sine_product<dim>;
+  }
   params.cfl = cfl;
   params.end_t = 1e9;
   params.device = device;
@@ -49,18 +65,19 @@ int run(int p, int n, int steps, double cfl, const char *out, double nitsche, in
 
 int main(int argc, char **argv) {
   if (argc < 7) {
-    std::fprintf(stderr, "usage: %s DIM P N STEPS CFL OUT [NITSCHE] [DEVICE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s DIM P N STEPS CFL OUT [NITSCHE] [DEVICE] [DATA]\n", argv[0]);
     return 2;
   }
   const int dim = std::atoi(argv[1]), p = std::atoi(argv[2]), n = std::atoi(argv[3]), steps = std::atoi(argv[4]);
   const double cfl = std::atof(argv[5]);
   const double nitsche = argc > 7 ? std::atof(argv[7]) : 0.0;
   const int device = argc > 8 ? std::atoi(argv[8]) : 0;
+  const int data = argc > 9 ? std::atoi(argv[9]) : 0;
   try {
     switch (dim) {
-      case 1: return run<1>(p, n, steps, cfl, argv[6], nitsche, device);
-      case 2: return run<2>(p, n, steps, cfl, argv[6], nitsche, device);
-      case 3: return run<3>(p, n, steps, cfl, argv[6], nitsche, device);
+      case 1: return run<1>(p, n, steps, cfl, argv[6], nitsche, device, data);
+      case 2: return run<2>(p, n, steps, cfl, argv[6], nitsche, device, data);
+      case 3: return run<3>(p, n, steps, cfl, argv[6], nitsche, device, data);
       default: std::fprintf(stderr, "dim must be 1, 2 or 3\n"); return 2;
     }
   } catch (const GDM::HIP::Error &e) {

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GDM_HIP_ABI_VERSION 17
+#define GDM_HIP_ABI_VERSION 18
 
 enum gdm_status {
   GDM_OK = 0,
@@ -472,6 +472,73 @@ int gdm_add_boundary_fn(gdm_op *op, double *dst_owned, int fn_kind, const double
  * ---------------------------------------------------------------------- */
 int gdm_error_norms(gdm_op *op, const double *u_local, int fn_kind, const double *params, int n_params, double t,
                     double *cell_errors, double *norms_host);
+
+/* ------------------------------------------------------------------------
+ * Forcing and Dirichlet data of the uncut wave / heat operator (ABI 18): the
+ * two data terms of StiffnessMatrixOperator::compute_rhs(dst, src,
+ * compute_impl_part, time) (applications/wave/include/gdm/wave/stiffness.h:
+ * 409-420, body :151-330) next to the operator part gdm_apply computes:
+ *   the source term (v, f(., t)) over QGauss(p+1)                 (:196-200)
+ *   the Nitsche data <gamma_D / h v - dv/dn, g_D(., t)> on the box (:320-326)
+ * Every call ADDS into dst_owned, as compute_rhs accumulates.  Single rank,
+ * non-periodic, any operator kind (the load is the right-hand side of an L2
+ * projection or a Poisson problem as well: tests/mass_01_gdm.cc,
+ * tests/poisson_01_gdm.cc).
+ *
+ *   gdm_add_load_fn      dst += scale (v, f), f a built-in gdm_fn_kind at time t
+ *                        (derivative 0) or its d/dt (derivative 1); kinds,
+ *                        params and formulas as gdm_eval_boundary.
+ *                        GDM_FN_CONSTANT and GDM_FN_SINE_PRODUCT are products
+ *                        of one-variable functions, for which tensor Gauss
+ *                        quadrature factorises exactly: (v, f) = b_z (x) b_y (x)
+ *                        b_x with the 1D load vectors b_d[i] = sum_q w_q h
+ *                        phi_i(x_q) f_d(x_q) (gdm_load_vector_1d); one term for
+ *                        the value, dim terms for d/dt (sum_e P_e cos_e prod_{d
+ *                        != e} sin_d, P_e = -2 pi k_e a_e).  The call reads and
+ *                        writes dst once.  GDM_FN_CONE is evaluated pointwise
+ *                        by the general kernel of gdm_add_load (d/dt = 0).
+ *                        scale == 0, and a derivative that is identically
+ *                        zero, launch nothing.
+ *   gdm_add_load         dst += scale (v, f) with f given by the caller as a
+ *                        DEVICE array on the tensor Gauss grid:
+ *                        fq[(qz Q_y + qy) Q_x + qx], Q_d = n_sub_d (p+1),
+ *                        q_d = cell_d (p+1) + point, x fastest, Q_d = 1 for
+ *                        d >= dim; the abscissae along d are entries 1 .. Q_d
+ *                        of gdm_field_points(mesh, d).  The array holds
+ *                        8 (p+1)^dim bytes per cell, about as much per DoF
+ *                        (1.7 KB at p = 5, 4 KB at p = 7 in 3D): the form for
+ *                        moderate meshes and for data no built-in function
+ *                        describes.  No intermediate grid is stored.
+ *   gdm_add_dirichlet_data
+ *                        dst += sum over the box faces of <gamma / h_min v -
+ *                        dv/dn, g>, gamma the operator's Nitsche parameter,
+ *                        h_min = min_d h_d (the cell's minimum vertex
+ *                        distance, as in the operator part).  g_bc: device
+ *                        array of n_bc_points values in the device block(0)
+ *                        order (gdm_bc_points, gdm_bc_reference_order;
+ *                        gdm_eval_boundary fills it for a built-in g).
+ *                        GDM_OP_WAVE operators created with nitsche > 0 only
+ *                        (GDM_ERR_UNSUPPORTED otherwise).
+ *   gdm_load_vector_1d   pure host: b_host [n_sub + 1] = the 1D load vector
+ *                        along `axis` for f sampled at the Gauss entries of
+ *                        gdm_field_points (f has its n_sub (p+1) + 2 entries,
+ *                        the two end values are not read; NULL: f = 1)
+ *   gdm_load_tile        pure host: the (x, y) node tile and the z chunk of
+ *                        node planes of the general load kernel, kernel axes
+ *                        (3D: x, y, z; 2D: x, y, -; 1D: -, -, x)
+ * GDM_ERR_UNSUPPORTED: n_ranks > 1, a periodic mesh, the inner operator of a
+ * cut handle.  GDM_ERR_ARG: NULL vectors, derivative outside {0, 1}, the
+ * parameter checks of gdm_eval_boundary.  All tables and scratch are built by
+ * gdm_op_create; no call allocates, so a first call may be captured in a
+ * hipGraph (t and scale are launch arguments, frozen at capture).  Gather
+ * form throughout: the bits of a result do not depend on the launch.
+ * ---------------------------------------------------------------------- */
+int gdm_add_load_fn(gdm_op *op, int fn_kind, const double *params, int n_params, double t, int derivative,
+                    double scale, double *dst_owned);
+int gdm_add_load(gdm_op *op, const double *fq, double scale, double *dst_owned);
+int gdm_add_dirichlet_data(gdm_op *op, const double *g_bc, double *dst_owned);
+int gdm_load_vector_1d(const gdm_mesh_desc *mesh, int axis, const double *f, double *b_host);
+int gdm_load_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
 
 /* memory helpers for callers without their own device allocator */
 int gdm_malloc(gdm_op *op, size_t bytes, void **ptr);
