@@ -19,6 +19,7 @@
 #include "gdm_coeffs.h"
 #include "gdm_kernels.h"
 #include "gdm_load.h"
+#include "gdm_fastdiag.h"
 #include "gdm_periodic.h"
 #include "gdm_post.h"
 #include "gdm_rk.h"
@@ -209,6 +210,16 @@ struct gdm_op {
   // the per-axis (sin, cos) load vectors of the rank-1 path [3][2][load_ld]
   double *load_Sw = nullptr, *load_bvec = nullptr;
   int load_ld = 0;
+  // fast diagonalisation (gdm_system_solve_setup): per kernel axis the tables
+  // S and S^T (row-major N x N) and lambda, the eigenvalue extremes for the
+  // host check of a solve, two scratch vectors
+  struct FastDiag {
+    bool built = false;
+    double *S[3] = {nullptr, nullptr, nullptr}, *St[3] = {nullptr, nullptr, nullptr};
+    double *lam[3] = {nullptr, nullptr, nullptr};
+    double lam_min[3] = {0, 0, 0}, lam_max[3] = {0, 0, 0};
+    double *tmp[2] = {nullptr, nullptr};
+  } fd;
 };
 
 namespace {
@@ -352,6 +363,15 @@ LineTables build_line_tables(gdm_op *op, const gdm::Band &M) {
   return t;
 }
 
+// gamma / h_min of the box Nitsche terms, h_min the smallest cell width over
+// the mesh's directions (0: no Nitsche terms)
+double nitsche_over_hmin(const gdm_mesh_desc *mesh, double nitsche) {
+  if (!(nitsche > 0.0)) return 0.0;
+  double hmin = 1e300;
+  for (int e = 0; e < mesh->dim; ++e) hmin = std::min(hmin, (mesh->hi[e] - mesh->lo[e]) / mesh->n_subdivisions[e]);
+  return nitsche / hmin;
+}
+
 void build_tables(gdm_op *op) {
   const int p = op->p;
   gdm::Band M[3], B[3];
@@ -389,28 +409,8 @@ void build_tables(gdm_op *op) {
       case GDM_OP_WAVE: {
         // -(grad v, grad u) (wave/stiffness.h:171-181) + box Nitsche
         // (:296-310): -[-dv/dn u - v du/dn + gamma/h v u] on each box face
-        for (int i = 0; i < n; ++i)
-          for (int j = std::max(0, i - p); j <= std::min(last, i + p); ++j) b(i, j) = -m.L(i, j);
-        if (op->nitsche > 0.0) {
-          double hmin = 1e300;
-          for (int e = 0; e < op->dim; ++e)
-            hmin = std::min(hmin, (op->mesh.hi[e] - op->mesh.lo[e]) / op->mesh.n_subdivisions[e]);
-          // traces of the boundary cells
-          const unsigned cl = 0, cr = ncell - 1;
-          const int catl = (int)gdm::category(cl, p, ncell), catr = (int)gdm::category(cr, p, ncell);
-          const int offl = (int)gdm::box_offset(cl, p, ncell), offr = (int)gdm::box_offset(cr, p, ncell);
-          for (int side = 0; side < 2; ++side) {
-            const int cat = side ? catr : catl, off = side ? offr : offl;
-            const double x = side ? 1.0 : 0.0, nrm = side ? 1.0 : -1.0;
-            for (int ii = 0; ii <= p; ++ii)
-              for (int jj = 0; jj <= p; ++jj) {
-                const double vi = gdm::shape_1d(p, cat, ii, x, 0), vj = gdm::shape_1d(p, cat, jj, x, 0);
-                const double di = gdm::shape_1d(p, cat, ii, x, 1) / h * nrm;
-                const double dj = gdm::shape_1d(p, cat, jj, x, 1) / h * nrm;
-                b(off + ii, off + jj) -= (-di * vj - vi * dj + op->nitsche / hmin * vi * vj);
-              }
-          }
-        }
+        // (gdm::wave_band_1d, shared with the fast diagonalisation)
+        b = gdm::wave_band_1d(p, ncell, h, nitsche_over_hmin(&op->mesh, op->nitsche), m);
         break;
       }
       default:
@@ -2787,6 +2787,187 @@ int gdm_load_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk
   if (tile_y) *tile_y = gdmk::LOAD_TY;
   if (z_chunk) *z_chunk = gdmk::LOAD_ZC;
   return GDM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// shared refusals of the fast-diagonalisation entry points; 0 = ok
+int check_fastdiag_op(gdm_op *op, const char *what, bool need_setup) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_WAVE)
+    return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": wave operators only (the stiffness matrix must be symmetric)");
+  if (op->mesh.n_ranks > 1) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": single rank only");
+  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": not with periodic constraints");
+  if (op->cut_inner) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": not on the inner operator of a cut handle");
+  if (need_setup && !op->fd.built)
+    return fail(GDM_ERR_STATE, std::string(what) + ": call gdm_system_solve_setup first");
+  return GDM_OK;
+}
+
+void fastdiag_host_tables(const gdm_mesh_desc *mesh, double nitsche, int axis, std::vector<double> &S,
+                          std::vector<double> &lambda) {
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  const double h = (mesh->hi[axis] - mesh->lo[axis]) / nc;
+  gdm::fastdiag_1d(mesh->fe_degree, nc, h, nitsche_over_hmin(mesh, nitsche), S, lambda);
+}
+
+// one pass along kernel axis ax: dst = T src, T = S (transpose 0) or S^T (1)
+gdmk::FastdiagPass fastdiag_pass(const gdm_op *op, int ax, int transpose) {
+  gdmk::FastdiagPass P{};
+  P.N = op->K[ax];
+  P.Tt = transpose ? op->fd.S[ax] : op->fd.St[ax];
+  P.K0 = op->K[0];
+  P.K1 = op->K[1];
+  if (ax == 0) {
+    P.row_form = 1;
+    P.cols = 1;
+    P.batch = (int64_t)op->K[1] * op->K[2];
+  } else {
+    P.cols = ax == 1 ? op->K[0] : (int64_t)op->K[0] * op->K[1];
+    P.batch = ax == 1 ? op->K[2] : 1;
+  }
+  return P;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gdm_fastdiag_tables(const gdm_mesh_desc *mesh, double nitsche, int axis, double *S_host, double *lambda_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  if (!S_host || !lambda_host) return fail(GDM_ERR_ARG, "S_host / lambda_host is NULL");
+  if (!std::isfinite(nitsche)) return fail(GDM_ERR_ARG, "nitsche is not finite");
+  for (int d = 0; d < mesh->dim; ++d)
+    if (mesh->n_subdivisions[d] < 1 || !(mesh->hi[d] > mesh->lo[d])) return fail(GDM_ERR_ARG, "empty box");
+  GDM_GUARD_BEGIN
+  std::vector<double> S, lambda;
+  fastdiag_host_tables(mesh, nitsche, axis, S, lambda);
+  std::copy(S.begin(), S.end(), S_host);
+  std::copy(lambda.begin(), lambda.end(), lambda_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_system_solve_setup(gdm_op *op) {
+  if (int rc = check_fastdiag_op(op, "gdm_system_solve_setup", false)) return rc;
+  if (op->fd.built) return GDM_OK;
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  // everything is uploaded before the handle changes: a failure leaves it as it was
+  gdm_op::FastDiag nf;
+  std::vector<void *> made;
+  auto up = [&](const std::vector<double> &h) {
+    double *d = dev_upload(h);
+    made.push_back(d);
+    return d;
+  };
+  try {
+    for (int ax = 0; ax < 3; ++ax) {
+      const int d = op->kdir[ax];
+      if (d < 0) continue;
+      std::vector<double> S, lambda;
+      fastdiag_host_tables(&op->mesh, op->nitsche, d, S, lambda);
+      const int n = (int)lambda.size();
+      std::vector<double> St((size_t)n * n);
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
+      nf.S[ax] = up(S);
+      nf.St[ax] = up(St);
+      nf.lam[ax] = up(lambda);
+      nf.lam_min[ax] = lambda.front();
+      nf.lam_max[ax] = lambda.back();
+    }
+    for (int i = 0; i < 2; ++i) {
+      double *t = nullptr;
+      hip_check(hipMalloc(&t, std::max<size_t>((size_t)op->layout.n_owned, 1) * sizeof(double)), "hipMalloc");
+      made.push_back(t);
+      nf.tmp[i] = t;
+    }
+  } catch (...) {
+    for (void *ptr : made) (void)hipFree(ptr);
+    throw;
+  }
+  for (void *ptr : made) op->allocations.push_back(ptr);
+  nf.built = true;
+  op->fd = nf;
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *src_owned, double *dst_owned) {
+  if (int rc = check_fastdiag_op(op, "gdm_fastdiag_transform", true)) return rc;
+  if (!src_owned || !dst_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  if (src_owned == dst_owned) return fail(GDM_ERR_ARG, "gdm_fastdiag_transform: src and dst must be distinct vectors");
+  if (axis < 0 || axis >= op->dim) return fail(GDM_ERR_ARG, "axis outside [0, dim)");
+  if (transpose != 0 && transpose != 1) return fail(GDM_ERR_ARG, "transpose must be 0 or 1");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  int ax = 0;
+  while (op->kdir[ax] != axis) ++ax;
+  hip_check(gdmk_launch_fastdiag_pass(fastdiag_pass(op, ax, transpose), src_owned, dst_owned, op->stream),
+            "fastdiag pass");
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned) {
+  if (int rc = check_fastdiag_op(op, "gdm_system_solve", true)) return rc;
+  if (!rhs_owned || !x_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_system_solve: alpha / tau is not finite");
+  // the spectrum of alpha M + tau S in the M-orthonormal eigenbasis is alpha + tau sum_d lambda_d
+  double smin = 0.0, smax = 0.0;
+  int axes[3], n_axes = 0;
+  for (int ax = 0; ax < 3; ++ax) {
+    if (op->kdir[ax] < 0) continue;
+    axes[n_axes++] = ax;
+    smin += op->fd.lam_min[ax];
+    smax += op->fd.lam_max[ax];
+  }
+  const double e0 = alpha + tau * smin, e1 = alpha + tau * smax;
+  const double lo = std::min(e0, e1), hi = std::max(e0, e1);
+  const double near0 = std::min(std::fabs(lo), std::fabs(hi)), far0 = std::max(std::fabs(lo), std::fabs(hi));
+  if ((lo <= 0.0 && hi >= 0.0) || near0 < 1e-12 * far0) {
+    char msg[320];
+    const double tiny = 1e-10 * std::max(std::fabs(smin), std::fabs(smax));
+    if (smin < -tiny)
+      std::snprintf(msg, sizeof msg,
+                    "gdm_system_solve: the stiffness matrix is indefinite (smallest eigenvalue %.6g): the Nitsche "
+                    "penalty %g is too small for degree %d; alpha M + tau S has eigenvalues in [%.6g, %.6g]",
+                    smin, op->nitsche, op->p, lo, hi);
+    else
+      std::snprintf(msg, sizeof msg,
+                    "gdm_system_solve: alpha M + tau S is singular (eigenvalues in [%.6g, %.6g]); without Nitsche "
+                    "terms the stiffness matrix has the constants in its kernel (pure Neumann problem)",
+                    lo, hi);
+    return fail(GDM_ERR_ARG, msg);
+  }
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  // forward S^T along x, y, z (the last one scales by the inverse eigenvalues),
+  // backward S along z, y, x; ping-pong between the two scratch vectors, so rhs
+  // is read by the first pass only and x written by the last only
+  const int n_pass = 2 * n_axes;
+  const double *src = rhs_owned;
+  for (int i = 0; i < n_pass; ++i) {
+    const bool fwd = i < n_axes;
+    const int ax = fwd ? axes[i] : axes[n_pass - 1 - i];
+    gdmk::FastdiagPass P = fastdiag_pass(op, ax, fwd ? 1 : 0);
+    if (i == n_axes - 1) {
+      P.scale = 1;
+      P.alpha = alpha;
+      P.tau = tau;
+      P.lam0 = op->fd.lam[0];
+      P.lam1 = op->fd.lam[1];
+      P.lam2 = op->fd.lam[2];
+    }
+    double *dst = i == n_pass - 1 ? x_owned : op->fd.tmp[i & 1];
+    hip_check(gdmk_launch_fastdiag_pass(P, src, dst, op->stream), "fastdiag pass");
+    src = dst;
+  }
+  return GDM_OK;
+  GDM_GUARD_END
 }
 
 int gdm_vec_dot(gdm_op *op, int64_t n, const double *x, const double *y, double *result_host) {

@@ -216,6 +216,225 @@ void cholesky_band(const Band &M, std::vector<double> &lrow, std::vector<double>
   }
 }
 
+Band wave_band_1d(int p, unsigned n_cells, double h, double nitsche_over_hmin, const Matrices1D &m) {
+  const int n = m.M.n, last = n - 1;
+  Band b(n, p);
+  for (int i = 0; i < n; ++i)
+    for (int j = std::max(0, i - p); j <= std::min(last, i + p); ++j) b(i, j) = -m.L(i, j);
+  if (nitsche_over_hmin > 0.0) {
+    // traces of the boundary cells
+    const unsigned cl = 0, cr = n_cells - 1;
+    const int catl = (int)category(cl, p, n_cells), catr = (int)category(cr, p, n_cells);
+    const int offl = (int)box_offset(cl, p, n_cells), offr = (int)box_offset(cr, p, n_cells);
+    for (int side = 0; side < 2; ++side) {
+      const int cat = side ? catr : catl, off = side ? offr : offl;
+      const double x = side ? 1.0 : 0.0, nrm = side ? 1.0 : -1.0;
+      for (int ii = 0; ii <= p; ++ii)
+        for (int jj = 0; jj <= p; ++jj) {
+          const double vi = shape_1d(p, cat, ii, x, 0), vj = shape_1d(p, cat, jj, x, 0);
+          const double di = shape_1d(p, cat, ii, x, 1) / h * nrm;
+          const double dj = shape_1d(p, cat, jj, x, 1) / h * nrm;
+          b(off + ii, off + jj) -= (-di * vj - vi * dj + nitsche_over_hmin * vi * vj);
+        }
+    }
+  }
+  return b;
+}
+
+// Householder tridiagonalisation followed by the implicit QL iteration (the
+// classic tred2 / tql2 pair).  V(k, j) = a[j * n + k]: every inner loop of
+// both phases then runs along contiguous memory.
+void symmetric_eigen(int n, std::vector<double> &a, std::vector<double> &d) {
+  d.assign(n, 0.0);
+  if (n == 0) return;
+  std::vector<double> e(n, 0.0);
+  auto V = [&](int k, int j) -> double & { return a[(size_t)j * n + k]; };
+  // -- tridiagonalise -------------------------------------------------------
+  for (int j = 0; j < n; ++j) d[j] = V(n - 1, j);
+  for (int i = n - 1; i > 0; --i) {
+    double scale = 0.0, h = 0.0;
+    for (int k = 0; k < i; ++k) scale += std::fabs(d[k]);
+    if (scale == 0.0) {
+      e[i] = d[i - 1];
+      for (int j = 0; j < i; ++j) {
+        d[j] = V(i - 1, j);
+        V(i, j) = 0.0;
+        V(j, i) = 0.0;
+      }
+    } else {
+      for (int k = 0; k < i; ++k) {
+        d[k] /= scale;
+        h += d[k] * d[k];
+      }
+      double f = d[i - 1];
+      double g = std::sqrt(h);
+      if (f > 0) g = -g;
+      e[i] = scale * g;
+      h -= f * g;
+      d[i - 1] = f - g;
+      for (int j = 0; j < i; ++j) e[j] = 0.0;
+      for (int j = 0; j < i; ++j) {
+        f = d[j];
+        V(j, i) = f;
+        g = e[j] + V(j, j) * f;
+        for (int k = j + 1; k <= i - 1; ++k) {
+          g += V(k, j) * d[k];
+          e[k] += V(k, j) * f;
+        }
+        e[j] = g;
+      }
+      f = 0.0;
+      for (int j = 0; j < i; ++j) {
+        e[j] /= h;
+        f += e[j] * d[j];
+      }
+      const double hh = f / (h + h);
+      for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
+      for (int j = 0; j < i; ++j) {
+        f = d[j];
+        g = e[j];
+        for (int k = j; k <= i - 1; ++k) V(k, j) -= (f * e[k] + g * d[k]);
+        d[j] = V(i - 1, j);
+        V(i, j) = 0.0;
+      }
+    }
+    d[i] = h;
+  }
+  // accumulate the transformations
+  for (int i = 0; i < n - 1; ++i) {
+    V(n - 1, i) = V(i, i);
+    V(i, i) = 1.0;
+    const double h = d[i + 1];
+    if (h != 0.0) {
+      for (int k = 0; k <= i; ++k) d[k] = V(k, i + 1) / h;
+      for (int j = 0; j <= i; ++j) {
+        double g = 0.0;
+        for (int k = 0; k <= i; ++k) g += V(k, i + 1) * V(k, j);
+        for (int k = 0; k <= i; ++k) V(k, j) -= g * d[k];
+      }
+    }
+    for (int k = 0; k <= i; ++k) V(k, i + 1) = 0.0;
+  }
+  for (int j = 0; j < n; ++j) {
+    d[j] = V(n - 1, j);
+    V(n - 1, j) = 0.0;
+  }
+  V(n - 1, n - 1) = 1.0;
+  e[0] = 0.0;
+  // -- implicit QL ------------------------------------------------------------
+  for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+  e[n - 1] = 0.0;
+  double f = 0.0, tst1 = 0.0;
+  const double eps = std::ldexp(1.0, -52);
+  for (int l = 0; l < n; ++l) {
+    tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
+    int m = l;
+    while (m < n - 1 && std::fabs(e[m]) > eps * tst1) ++m;
+    if (m > l) {
+      int iter = 0;
+      do {
+        if (++iter > 200) throw std::runtime_error("symmetric_eigen: the QL iteration did not converge");
+        double g = d[l];
+        double p = (d[l + 1] - g) / (2.0 * e[l]);
+        double r = std::hypot(p, 1.0);
+        if (p < 0) r = -r;
+        d[l] = e[l] / (p + r);
+        d[l + 1] = e[l] * (p + r);
+        const double dl1 = d[l + 1];
+        double h = g - d[l];
+        for (int i = l + 2; i < n; ++i) d[i] -= h;
+        f += h;
+        p = d[m];
+        double c = 1.0, c2 = c, c3 = c;
+        const double el1 = e[l + 1];
+        double s = 0.0, s2 = 0.0;
+        for (int i = m - 1; i >= l; --i) {
+          c3 = c2;
+          c2 = c;
+          s2 = s;
+          g = c * e[i];
+          h = c * p;
+          r = std::hypot(p, e[i]);
+          e[i + 1] = s * r;
+          s = e[i] / r;
+          c = p / r;
+          p = c * d[i] - s * g;
+          d[i + 1] = h + s * (c * g + s * d[i]);
+          double *vi = &a[(size_t)i * n], *vi1 = &a[(size_t)(i + 1) * n];
+          for (int k = 0; k < n; ++k) {
+            h = vi1[k];
+            vi1[k] = s * vi[k] + c * h;
+            vi[k] = c * vi[k] - s * h;
+          }
+        }
+        p = -s * s2 * c3 * el1 * e[l] / dl1;
+        e[l] = s * p;
+        d[l] = c * p;
+      } while (std::fabs(e[l]) > eps * tst1);
+    }
+    d[l] = d[l] + f;
+    e[l] = 0.0;
+  }
+  // ascending order
+  for (int i = 0; i < n - 1; ++i) {
+    int k = i;
+    for (int j = i + 1; j < n; ++j)
+      if (d[j] < d[k]) k = j;
+    if (k != i) {
+      std::swap(d[k], d[i]);
+      std::swap_ranges(&a[(size_t)i * n], &a[(size_t)i * n] + n, &a[(size_t)k * n]);
+    }
+  }
+}
+
+void fastdiag_1d(int p, unsigned n_cells, double h, double nitsche_over_hmin, std::vector<double> &S,
+                 std::vector<double> &lambda) {
+  const Matrices1D m = assemble_1d(p, n_cells, h);
+  const Band B = wave_band_1d(p, n_cells, h, nitsche_over_hmin, m);
+  const int n = m.M.n, hb = m.M.hb, wl = hb + 1;
+  std::vector<double> lrow, invd;
+  cholesky_band(m.M, lrow, invd);
+  auto R = [&](int i, int j) { return lrow[(size_t)i * wl + (j - i + hb)]; };  // i - hb <= j <= i
+  // forward substitution R y = x in place, x a contiguous vector
+  auto forward = [&](double *x) {
+    for (int i = 0; i < n; ++i) {
+      double s = x[i];
+      for (int j = std::max(0, i - hb); j < i; ++j) s -= R(i, j) * x[j];
+      x[i] = s * invd[i];
+    }
+  };
+  // c[j * n + i]: column j of A, then of R^-1 A; transposed, again: R^-1 (R^-1 A)^T = R^-1 A R^-T
+  std::vector<double> c((size_t)n * n, 0.0), t((size_t)n * n);
+  for (int j = 0; j < n; ++j) {
+    for (int i = std::max(0, j - hb); i <= std::min(n - 1, j + hb); ++i) c[(size_t)j * n + i] = -B(i, j);
+    forward(&c[(size_t)j * n]);
+  }
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i < n; ++i) t[(size_t)i * n + j] = c[(size_t)j * n + i];
+  for (int j = 0; j < n; ++j) forward(&t[(size_t)j * n]);
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i <= j; ++i) {
+      const double v = 0.5 * (t[(size_t)j * n + i] + t[(size_t)i * n + j]);
+      t[(size_t)j * n + i] = t[(size_t)i * n + j] = v;
+    }
+  symmetric_eigen(n, t, lambda);
+  // S = R^-T Q column by column (back substitution), signs fixed
+  S.assign((size_t)n * n, 0.0);
+  for (int j = 0; j < n; ++j) {
+    double *x = &t[(size_t)j * n];
+    for (int i = n - 1; i >= 0; --i) {
+      double s = x[i];
+      for (int k = i + 1; k <= std::min(n - 1, i + hb); ++k) s -= R(k, i) * x[k];
+      x[i] = s * invd[i];
+    }
+    int big = 0;
+    for (int i = 1; i < n; ++i)
+      if (std::fabs(x[i]) > std::fabs(x[big])) big = i;
+    const double sg = x[big] < 0.0 ? -1.0 : 1.0;
+    for (int i = 0; i < n; ++i) S[(size_t)i * n + j] = sg * x[i];
+  }
+}
+
 FaceTable face_table_1d(int p, unsigned n_cells, double h, unsigned cell_begin, unsigned cell_end) {
   FaceTable t;
   const int n1 = p + 1;

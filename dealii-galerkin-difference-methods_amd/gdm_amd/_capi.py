@@ -169,6 +169,10 @@ def load():
         "gdm_load_vector_1d": [ctypes.POINTER(MeshDesc), i32, P, P],
         "gdm_load_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                           ctypes.POINTER(ctypes.c_int)],
+        "gdm_fastdiag_tables": [ctypes.POINTER(MeshDesc), d, i32, P, P],
+        "gdm_system_solve_setup": [P],
+        "gdm_system_solve": [P, d, d, P, P],
+        "gdm_fastdiag_transform": [P, i32, i32, P, P],
         "gdm_mass_spike_eps": [P, P],
         "gdm_mass_solve_slab": [P, P, P],
         "gdm_mass_solve_interface": [P, P],
@@ -330,6 +334,22 @@ def load_vector_1d(mesh, axis, f=None):
     check(load().gdm_load_vector_1d(ctypes.byref(mesh), int(axis), fp, b.ctypes.data_as(ctypes.c_void_p)),
           "gdm_load_vector_1d")
     return b
+
+
+def fastdiag_tables(mesh, nitsche, axis):
+    """(S, lambda) of the fast diagonalisation along `axis`: the generalised
+    eigenpairs A S = M S diag(lambda), S^T M S = I, of the wave operator's 1D
+    factor A = L + box Nitsche terms; S [N, N] (column j = eigenvector j),
+    lambda ascending.  Pure host, no GPU (gdm_fastdiag_tables)."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("fastdiag_tables: axis outside [0, dim)")
+    n = mesh.n_subdivisions[axis] + 1
+    S, lam = np.zeros((n, n)), np.zeros(n)
+    check(load().gdm_fastdiag_tables(ctypes.byref(mesh), float(nitsche), int(axis), S.ctypes.data_as(ctypes.c_void_p),
+                                     lam.ctypes.data_as(ctypes.c_void_p)), "gdm_fastdiag_tables")
+    return S, lam
 
 
 def load_tile(fe_degree, dim=3):

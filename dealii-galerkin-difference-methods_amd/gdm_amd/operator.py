@@ -59,6 +59,7 @@ class GdmOperator:
         self.dim, self.p = dim, fe_degree
         self.kind = KINDS[kind] if isinstance(kind, str) else kind
         self.device = device
+        self._params = tuple(float(v) for v in params)
         arr = (ctypes.c_double * max(1, len(params)))(*params) if len(params) else None
         h = ctypes.c_void_p()
         torch.cuda.set_device(device)
@@ -348,6 +349,42 @@ class GdmOperator:
     def load_tile(self):
         """(tile_x, tile_y, z_chunk) of the general load kernel, kernel axes"""
         return _capi.load_tile(self.p, self.dim)
+
+    # -- direct heat-implicit / Poisson solve (fast diagonalisation) -------------
+    @property
+    def nitsche(self):
+        """the Nitsche parameter of a wave operator (params[0]; 0 otherwise)"""
+        return float(self._params[0]) if self.kind == KINDS["wave"] and len(self._params) else 0.0
+
+    def fastdiag_tables(self, axis):
+        """(S, lambda) of direction `axis` on the host (gdm_fastdiag_tables)"""
+        return _capi.fastdiag_tables(self.mesh, self.nitsche, axis)
+
+    def system_solve_setup(self):
+        """Build and upload the fast-diagonalisation tables and the scratch
+        vectors (gdm_system_solve_setup; idempotent)"""
+        check(self.lib.gdm_system_solve_setup(self.h), "gdm_system_solve_setup")
+
+    def system_solve(self, alpha, tau, rhs_owned, x_owned=None):
+        """x = (alpha M - tau K)^-1 rhs, K = apply (gdm_system_solve):
+        heat-impl alpha = 1, tau = dt; Poisson alpha = 0, tau = 1.  x may be
+        rhs; None allocates it."""
+        if x_owned is None:
+            x_owned = self.new_vector(False)
+        self._check_sizes(None, rhs_owned)
+        self._check_sizes(None, x_owned)
+        check(self.lib.gdm_system_solve(self.h, float(alpha), float(tau), _ptr(rhs_owned), _ptr(x_owned)),
+              "gdm_system_solve")
+        return x_owned
+
+    def fastdiag_transform(self, axis, transpose, src_owned, dst_owned):
+        """dst = T src along `axis`, T = S (transpose 0) or S^T (1)
+        (gdm_fastdiag_transform)"""
+        self._check_sizes(None, src_owned)
+        self._check_sizes(None, dst_owned)
+        check(self.lib.gdm_fastdiag_transform(self.h, int(axis), int(transpose), _ptr(src_owned), _ptr(dst_owned)),
+              "gdm_fastdiag_transform")
+        return dst_owned
 
     def mass_solve_slab(self, rhs_owned, x_owned):
         """Distributed exact mass inverse, step 1: the slab-local solve

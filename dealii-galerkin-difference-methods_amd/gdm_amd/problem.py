@@ -153,6 +153,61 @@ class WaveProblem:
         return n
 
 
+class HeatProblem(WaveProblem):
+    """heat-impl and heat-rk on one rank and an uncut box (wave/problem.h:
+    210-279 and 72-128): M du/dt = K u + data(t), K the wave operator of `op`,
+    data(t) = (v, f(t)) + the Nitsche data of g_D(t) (WaveProblem.add_data;
+    forcing / dirichlet as there).
+
+    scheme "impl": backward Euler, (M + h S) u_new = M u + h data(t + h) with
+    S = -K, solved directly (GdmOperator.system_solve(1, h)); h is the
+    DiscreteTime step of every step, so a shorter last step needs no new setup.
+    scheme "rk": classic RK4 of du/dt = M^-1 (K u + data(t)) through apply +
+    mass_solve_rk."""
+
+    def __init__(self, op, forcing=None, dirichlet=None, scheme="impl"):
+        if scheme not in ("impl", "rk"):
+            raise GdmError("HeatProblem: scheme is 'impl' or 'rk'")
+        WaveProblem.__init__(self, op, forcing, dirichlet)
+        self.scheme = scheme
+        if scheme == "impl":
+            op.system_solve_setup()
+
+    def step(self, t, h):
+        op, u, k = self.op, self.u, self._kv
+        if self.scheme == "impl":
+            op.mass_apply(u, k)
+            if self.forcing is not None or self.dirichlet is not None:
+                data = self._Y[0]
+                data.zero_()
+                self.add_data(t + h, data)
+                op.axpby(h, data, 1.0, k)
+            op.system_solve(1.0, h, k, u)
+            return
+        acc, Y = self._acc[0], self._Y[0]
+        stage = u
+        for s in range(4):
+            op.apply(stage, k)
+            self.add_data(t + RK4_C[s] * h, k)
+            last = s == 3
+            op.mass_solve_rk(k, h * RK4_B[s], u if s == 0 else acc, u if last else acc,
+                             0.0 if last else h * RK4_A[s], None if last else u, None if last else Y)
+            stage = Y
+
+
+def solve_poisson(op, forcing=None, dirichlet=None, t=0.0):
+    """The "poisson" simulation type (wave/problem.h:46-71) on an uncut box:
+    the device solution of S u = data(t), S = -K of the wave operator `op`
+    (created with nitsche > 0: without the box Nitsche terms S is singular),
+    data as in WaveProblem (forcing / dirichlet)."""
+    prob = WaveProblem(op, forcing, dirichlet)
+    op.system_solve_setup()
+    rhs = prob._kv
+    rhs.zero_()
+    prob.add_data(t, rhs)
+    return op.system_solve(0.0, 1.0, rhs, prob.u)
+
+
 class AdvectionProblem:
     """advection problem.h:31-102 on one rank with a built-in boundary
     function (gdm_fn_kind) for g and dg/dt."""

@@ -42,6 +42,8 @@ struct Parameters {
   double cfl_pow = 1.0;
   int device = 0;
   int n_ranks = 1, rank = 0;
+  // "wave-rk" (problem.h:280-346), "heat-rk" (:72-128), "heat-impl" (:210-279) or "poisson" (:46-71)
+  std::string simulation_type = "wave-rk";
 };
 
 template <int dim>
@@ -139,6 +141,16 @@ class StiffnessMatrixOperator {
     }
   }
 
+  // The linear solves of "heat-impl" and "poisson" (problem.h:217-226, 263-269
+  // and :46-67): x = (alpha M + tau S)^-1 rhs with S = get_sparse_matrix() =
+  // -compute_rhs's operator part; the reference's CG + AMG on the assembled
+  // matrix is replaced by the engine's fast diagonalisation.  A changed tau
+  // (the last time step) needs no new setup.
+  void setup_system_solve() const { check(gdm_system_solve_setup(op), "gdm_system_solve_setup"); }
+  void system_solve(double alpha, double tau, double *x_owned, const double *rhs_owned) const {
+    check(gdm_system_solve(op, alpha, tau, rhs_owned, x_owned), "gdm_system_solve");
+  }
+
   gdm_op *handle() const { return op; }
   const gdm_layout &get_layout() const { return layout; }
   double *owned(VectorType &v) const { return v.get_values() + layout.ghost_planes_below * layout.plane_size; }
@@ -200,10 +212,16 @@ class MassMatrixOperator {
   gdm_layout layout{};
 };
 
-// WaveProblem<dim>::run, "wave-rk" (problem.h:280-346): y = (u, v),
-// du/dt = v, dv/dt = M^-1 compute_rhs(u, true, t), RK_CLASSIC_FOURTH_ORDER,
-// DiscreteTime(start, end, cfl dx^cfl_pow), device-resident in low-storage
-// form (gdm_vec_rk_update).
+// WaveProblem<dim>::run, dispatched on Parameters::simulation_type as the
+// reference's (problem.h:40-346):
+//   "wave-rk"   y = (u, v), du/dt = v, dv/dt = M^-1 compute_rhs(u, true, t),
+//               RK_CLASSIC_FOURTH_ORDER, DiscreteTime(start, end, cfl
+//               dx^cfl_pow), device-resident in low-storage form
+//               (gdm_vec_rk_update)
+//   "heat-rk"   du/dt = M^-1 compute_rhs(u, true, t), the same RK4
+//   "heat-impl" u := (M + h S)^-1 (M u + h compute_rhs(u, false, t + h)), h the
+//               DiscreteTime step of every step
+//   "poisson"   S u = compute_rhs(., false, 0); no time steps
 template <int dim>
 class WaveProblem {
  public:
@@ -217,9 +235,50 @@ class WaveProblem {
     stiffness_matrix_operator.reinit(params);
     const double delta_t = params.cfl * std::pow(discretization.get_dx(), params.cfl_pow);  // problem.h:284
     for (auto *v : {&u, &v_, &acc_u, &acc_v, &Yu, &Yv, &kv}) stiffness_matrix_operator.initialize_dof_vector(*v);
+    const std::string &type = params.simulation_type;
+    const StiffnessMatrixOperator<dim> &S = stiffness_matrix_operator;
+    if (type == "poisson") {
+      S.compute_rhs(kv, u, false, 0.0);
+      S.setup_system_solve();
+      S.system_solve(0.0, 1.0, S.owned(u), S.owned(kv));
+      return 0;
+    }
+    if (type != "wave-rk" && type != "heat-rk" && type != "heat-impl")
+      throw Error("WaveProblem: simulation_type is wave-rk, heat-rk, heat-impl or poisson");
     set_initial_condition(u);
     DiscreteTime time(params.start_t, params.end_t, delta_t);
     unsigned int n = 0;
+    if (type == "heat-impl") {
+      S.setup_system_solve();
+      const int64_t n_owned = S.get_layout().n_owned;
+      while (!time.is_at_end() && n < max_steps) {
+        const double t0 = time.get_current_time(), h = time.get_next_step_size();
+        // rhs = h compute_rhs(u, false, t0 + h) + M u
+        S.compute_rhs(acc_u, u, false, t0 + h);
+        mass_matrix_operator.vmult(S.owned(kv), u.get_values());
+        check(gdm_vec_axpby(S.handle(), n_owned, h, S.owned(acc_u), 1.0, S.owned(kv)), "gdm_vec_axpby");
+        S.system_solve(1.0, h, S.owned(u), S.owned(kv));
+        time.advance_time();
+        ++n;
+      }
+      return n;
+    }
+    if (type == "heat-rk") {
+      while (!time.is_at_end() && n < max_steps) {
+        const double t0 = time.get_current_time(), h = time.get_next_step_size();
+        const DeviceVector *su = &u;
+        for (int s = 0; s < 4; ++s) {
+          S.compute_rhs(kv, *su, true, t0 + ClassicRK4::c[s] * h);
+          double *r = S.owned(kv);
+          mass_matrix_operator.solve(r, r);
+          rk4_stage_update(s, h, kv, u, acc_u, Yu);
+          su = &Yu;
+        }
+        time.advance_time();
+        ++n;
+      }
+      return n;
+    }
     while (!time.is_at_end() && n < max_steps) {
       const double t0 = time.get_current_time(), h = time.get_next_step_size();
       const DeviceVector *su = &u, *sv = &v_;

@@ -2,15 +2,18 @@
 // the C++ mirror of the reference's wave operator surface (gdm/hip/wave.h), in
 // the shape of applications/wave/wave-app.cc:222-285 + problem.h:280-346.
 //
-//   wave_app DIM P N STEPS CFL OUT [NITSCHE] [DEVICE] [DATA]
+//   wave_app DIM P N STEPS CFL OUT [NITSCHE] [DEVICE] [DATA] [SIMULATION_TYPE]
 //
 // Box [-1.21, 1.21]^dim, initial displacement u0 = prod_d cos(0.75 pi x_d /
 // 1.21 + 0.2 d), v0 = 0, natural boundary (NITSCHE = 0) or box Nitsche with
 // gamma_D = NITSCHE.  DATA = 1 (needs NITSCHE > 0) drives the problem with
 // function_rhs = 3 w and function_domain_dbc = w, w(x, t) = prod_d sin(2 pi
 // k_d (x_d - a_d t) + phi_d), a = (0.8, 0, 0), k = (0.4, 0.3, 0.35), phi =
-// (0.3, 0.5, 0.2), and starts from u0 = w(., 0).  Writes u then v after STEPS
-// RK4 steps to OUT (raw little-endian doubles, reference global order).
+// (0.3, 0.5, 0.2), and starts from u0 = w(., 0).  SIMULATION_TYPE = wave-rk
+// (default), heat-rk, heat-impl or poisson (the latter two solve with the
+// stiffness matrix: NITSCHE > 0; poisson takes no steps, v stays 0 for all
+// three).  Writes u then v after STEPS steps to OUT (raw little-endian
+// doubles, reference global order).
 #include <gdm/hip/wave.h>
 
 #include <cstdio>
@@ -30,7 +33,8 @@ double sine_product(const GDM::HIP::Point &x, double t) {
 }
 
 template <int dim>
-int run(int p, int n, int steps, double cfl, const char *out, double nitsche, int device, int data) {
+int run(int p, int n, int steps, double cfl, const char *out, double nitsche, int device, int data,
+        const char *simulation_type) {
   GDM::HIP::Wave::Parameters<dim> params;
   params.fe_degree = p;
   params.n_subdivisions_1D = n;
@@ -48,6 +52,7 @@ int run(int p, int n, int steps, double cfl, const char *out, double nitsche, in
   params.cfl = cfl;
   params.end_t = 1e9;
   params.device = device;
+  params.simulation_type = simulation_type;
   GDM::HIP::Wave::WaveProblem<dim> problem(params);
   const unsigned int done = problem.run(steps);
   std::vector<double> u = problem.get_solution();
@@ -65,7 +70,7 @@ int run(int p, int n, int steps, double cfl, const char *out, double nitsche, in
 
 int main(int argc, char **argv) {
   if (argc < 7) {
-    std::fprintf(stderr, "usage: %s DIM P N STEPS CFL OUT [NITSCHE] [DEVICE] [DATA]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s DIM P N STEPS CFL OUT [NITSCHE] [DEVICE] [DATA] [SIMULATION_TYPE]\n", argv[0]);
     return 2;
   }
   const int dim = std::atoi(argv[1]), p = std::atoi(argv[2]), n = std::atoi(argv[3]), steps = std::atoi(argv[4]);
@@ -73,11 +78,12 @@ int main(int argc, char **argv) {
   const double nitsche = argc > 7 ? std::atof(argv[7]) : 0.0;
   const int device = argc > 8 ? std::atoi(argv[8]) : 0;
   const int data = argc > 9 ? std::atoi(argv[9]) : 0;
+  const char *type = argc > 10 ? argv[10] : "wave-rk";
   try {
     switch (dim) {
-      case 1: return run<1>(p, n, steps, cfl, argv[6], nitsche, device, data);
-      case 2: return run<2>(p, n, steps, cfl, argv[6], nitsche, device, data);
-      case 3: return run<3>(p, n, steps, cfl, argv[6], nitsche, device, data);
+      case 1: return run<1>(p, n, steps, cfl, argv[6], nitsche, device, data, type);
+      case 2: return run<2>(p, n, steps, cfl, argv[6], nitsche, device, data, type);
+      case 3: return run<3>(p, n, steps, cfl, argv[6], nitsche, device, data, type);
       default: std::fprintf(stderr, "dim must be 1, 2 or 3\n"); return 2;
     }
   } catch (const GDM::HIP::Error &e) {

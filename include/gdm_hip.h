@@ -540,6 +540,60 @@ int gdm_add_dirichlet_data(gdm_op *op, const double *g_bc, double *dst_owned);
 int gdm_load_vector_1d(const gdm_mesh_desc *mesh, int axis, const double *f, double *b_host);
 int gdm_load_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
 
+/* ------------------------------------------------------------------------
+ * Direct solve with the uncut wave / heat operator by fast diagonalisation
+ * (added within ABI 18: new entry points only, backward compatible, the
+ * version number is unchanged).  The linear solves of the "poisson" and
+ * "heat-impl" simulation types (applications/wave/include/gdm/wave/problem.h:
+ * 46-71, 210-279), where the reference runs CG + AMG on the assembled matrix.
+ * On an uncut box the stiffness matrix is S = -K = sum_d M (x) .. A_d .. (x) M
+ * with the symmetric 1D factors A_d = -B_d (the -L_d + box Nitsche band of
+ * gdm_apply).  With the generalised eigenpairs A_d S_d = M_d S_d Lambda_d,
+ * S_d^T M_d S_d = I:
+ *   (alpha M + tau S)^-1 = (S_z (x) S_y (x) S_x)
+ *                          diag(1 / (alpha + tau (lambda_z + lambda_y + lambda_x)))
+ *                          (S_z (x) S_y (x) S_x)^T
+ * -- 2 dim dense N_d x N_d contractions over the vector on the FP64 matrix
+ * pipe (csrc/gdm_fastdiag.hip), the diagonal scaling in the epilogue of the
+ * last forward pass.  Exact up to round-off ~ 1e-17 cond.
+ *
+ *   gdm_fastdiag_tables  pure host: S_host (row-major N x N, column j =
+ *                        eigenvector j) and lambda_host (N, ascending) of
+ *                        direction `axis`, N = n_subdivisions[axis] + 1;
+ *                        nitsche = the operator's Nitsche parameter (h_min is
+ *                        taken over the mesh's directions).  Each eigenvector's
+ *                        entry of largest magnitude is positive; two calls give
+ *                        the same bits.
+ *   gdm_system_solve_setup  builds and uploads the tables of every direction
+ *                        and two scratch vectors; idempotent.  The only call
+ *                        of the group that allocates or synchronises.
+ *   gdm_system_solve     x = (alpha M - tau K)^-1 rhs, K = gdm_apply of this op
+ *                        (K = -S of the reference): heat-impl alpha = 1, tau =
+ *                        dt (problem.h:217-226, 263-269; a changed last step
+ *                        needs no new setup); poisson alpha = 0, tau = 1
+ *                        (problem.h:46-67).  x_owned may equal rhs_owned; rhs
+ *                        is otherwise not modified.  No allocation, no host
+ *                        synchronisation: the call may be captured in a
+ *                        hipGraph (alpha, tau frozen at capture).  Bitwise
+ *                        repeatable.  Calls on one op share its scratch: order
+ *                        them on one stream.
+ *   gdm_fastdiag_transform  one pass, for tests and tools: dst = T src along
+ *                        `axis` (reference direction), T = S (transpose 0) or
+ *                        S^T (1); src and dst distinct.
+ * GDM_ERR_UNSUPPORTED: a kind other than GDM_OP_WAVE, n_ranks > 1, a periodic
+ * mesh, the inner operator of a cut handle.  GDM_ERR_STATE: solve / transform
+ * before setup.  GDM_ERR_ARG: NULL pointers, non-finite alpha or tau, axis
+ * outside [0, dim), and a singular or indefinite system: the interval [alpha +
+ * tau sum_d lambda_d,min, alpha + tau sum_d lambda_d,max] contains 0 or its end
+ * nearer to 0 is below 1e-12 of the other in magnitude (pure Neumann Poisson:
+ * nitsche = 0 with alpha = 0; a Nitsche penalty too small for the degree, e.g.
+ * gamma = 4 from p = 5 on).
+ * ---------------------------------------------------------------------- */
+int gdm_fastdiag_tables(const gdm_mesh_desc *mesh, double nitsche, int axis, double *S_host, double *lambda_host);
+int gdm_system_solve_setup(gdm_op *op);
+int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned);
+int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *src_owned, double *dst_owned);
+
 /* memory helpers for callers without their own device allocator */
 int gdm_malloc(gdm_op *op, size_t bytes, void **ptr);
 int gdm_free(gdm_op *op, void *ptr);
