@@ -19,6 +19,7 @@
 #include "gdm_coeffs.h"
 #include "gdm_kernels.h"
 #include "gdm_load.h"
+#include "gdm_elasticity.h"
 #include "gdm_fastdiag.h"
 #include "gdm_periodic.h"
 #include "gdm_post.h"
@@ -220,6 +221,21 @@ struct gdm_op {
     double lam_min[3] = {0, 0, 0}, lam_max[3] = {0, 0, 0};
     double *tmp[2] = {nullptr, nullptr};
   } fd;
+  // linear elasticity (GDM_OP_ELASTICITY): the Dirichlet-reduced 1D tables of
+  // the kernel (built by gdm_op_create), the diagonal, and the block
+  // fast-diagonalisation preconditioner (gdm_elasticity_precond_setup): per
+  // kernel axis S, S^T and per component the eigenvalues pre-scaled by w_cd
+  struct Elasticity {
+    double mu = 0.0, lambda = 0.0;
+    gdmk::ElasArgs args{};       // src / dst filled per apply
+    double *invdiag = nullptr;   // Jacobi: 1 / diag, built on first use
+    double *free_mask = nullptr; // 1 on free DoFs, 0 on constrained ones (first solve)
+    bool built = false;
+    double *S[3] = {nullptr, nullptr, nullptr}, *St[3] = {nullptr, nullptr, nullptr};
+    double *lam[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    double *tmp[2] = {nullptr, nullptr};
+    double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, b (masked rhs)
+  } el;
 };
 
 namespace {
@@ -966,6 +982,106 @@ int choose_zchunk(const gdm_op *op) {
   return std::max(1, zc);
 }
 
+// ---- linear elasticity (GDM_OP_ELASTICITY) ----
+
+// w[c][d]: weight of L_d in the diagonal block c of 2 mu (eps, eps) + lambda (div, div)
+void elasticity_weights(double mu, double lambda, double w[3][3]) {
+  for (int c = 0; c < 3; ++c)
+    for (int d = 0; d < 3; ++d) w[c][d] = c == d ? 2.0 * mu + lambda : mu;
+}
+
+gdm::ElasticityBands1D elasticity_bands(const gdm_mesh_desc *mesh, int d) {
+  const unsigned nc = (unsigned)mesh->n_subdivisions[d];
+  return gdm::elasticity_bands_1d(mesh->fe_degree, nc, (mesh->hi[d] - mesh->lo[d]) / nc);
+}
+
+// the kernel's table of one direction: [4][N][2p+1] in the order M, C, C^T, L
+std::vector<double> elasticity_table(const gdm::ElasticityBands1D &b) {
+  std::vector<double> t;
+  t.reserve(4 * b.M.a.size());
+  for (const gdm::Band *f : {&b.M, &b.C, &b.Ct, &b.L}) t.insert(t.end(), f->a.begin(), f->a.end());
+  return t;
+}
+
+// diag(P A P + I - P), component-major: C has a zero diagonal, so only the
+// diagonal blocks contribute, each a sum of products of 1D diagonals
+std::vector<double> elasticity_diagonal_host(const gdm_mesh_desc *mesh, double mu, double lambda) {
+  const int dim = mesh->dim;
+  double w[3][3];
+  elasticity_weights(mu, lambda, w);
+  std::vector<double> dm[3], dl[3];
+  int N[3] = {1, 1, 1};
+  for (int d = 0; d < 3; ++d) {
+    if (d >= dim) {
+      dm[d].assign(1, 1.0);
+      dl[d].assign(1, 0.0);
+      continue;
+    }
+    const gdm::ElasticityBands1D b = elasticity_bands(mesh, d);
+    N[d] = b.M.n;
+    dm[d].resize(N[d]);
+    dl[d].resize(N[d]);
+    for (int i = 0; i < N[d]; ++i) {
+      dm[d][i] = b.M(i, i);
+      dl[d][i] = b.L(i, i);
+    }
+  }
+  const int64_t n = (int64_t)N[0] * N[1] * N[2];
+  std::vector<double> out((size_t)(n * dim));
+  for (int c = 0; c < dim; ++c)
+    for (int i2 = 0; i2 < N[2]; ++i2)
+      for (int i1 = 0; i1 < N[1]; ++i1)
+        for (int i0 = 0; i0 < N[0]; ++i0) {
+          const int id[3] = {i0, i1, i2};
+          bool constrained = false;
+          for (int d = 0; d < dim; ++d) constrained = constrained || id[d] == 0 || id[d] == N[d] - 1;
+          double s = 0.0;
+          for (int d = 0; d < dim; ++d) {
+            double t = w[c][d];
+            for (int e = 0; e < dim; ++e) t *= e == d ? dl[e][id[e]] : dm[e][id[e]];
+            s += t;
+          }
+          out[(size_t)(c * n + ((int64_t)i2 * N[1] + i1) * N[0] + i0)] = constrained ? 1.0 : s;
+        }
+  return out;
+}
+
+// 1 on the free DoFs, 0 on the constrained ones, component-major
+std::vector<double> elasticity_mask_host(const gdm_op *op) {
+  const int64_t n = op->layout.n_owned;
+  std::vector<double> m((size_t)(n * op->dim));
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t id[3] = {i % op->N[0], (i / op->N[0]) % op->N[1], i / ((int64_t)op->N[0] * op->N[1])};
+    bool constrained = false;
+    for (int d = 0; d < op->dim; ++d) constrained = constrained || id[d] == 0 || id[d] == op->N[d] - 1;
+    for (int c = 0; c < op->dim; ++c) m[(size_t)(c * n + i)] = constrained ? 0.0 : 1.0;
+  }
+  return m;
+}
+
+void build_elasticity(gdm_op *op) {
+  gdmk::ElasArgs &A = op->el.args;
+  const double *tab[3] = {nullptr, nullptr, nullptr};
+  for (int d = 0; d < op->dim; ++d) tab[d] = keep(op, dev_upload(elasticity_table(elasticity_bands(&op->mesh, d))));
+  A.xtab = tab[0];
+  A.ytab = tab[1];
+  A.ztab = tab[2];
+  A.Nx = op->K[0];
+  A.Ny = op->K[1];
+  A.Nz = op->K[2];
+  A.comp_stride = op->layout.n_owned;
+  A.mu = op->el.mu;
+  A.lambda = op->el.lambda;
+  elasticity_weights(op->el.mu, op->el.lambda, A.w);
+}
+
+void elasticity_apply(gdm_op *op, const double *src, double *dst) {
+  gdmk::ElasArgs A = op->el.args;
+  A.src = src;
+  A.dst = dst;
+  hip_check(gdmk::launch_elasticity(op->p, op->dim, A, op->stream), "elasticity launch");
+}
+
 #define GDM_GUARD_BEGIN try {
 #define GDM_GUARD_END                                             \
   }                                                               \
@@ -1451,7 +1567,15 @@ int gdm_op_create(const gdm_mesh_desc *mesh, int kind, const double *params, int
   if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
   if (p < 1 || p > 9 || p % 2 == 0)
     return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9] (fe.h:321-323 tabulates odd p only)");
-  if (kind < GDM_OP_MASS || kind > GDM_OP_CONVECTIVE) return fail(GDM_ERR_ARG, "unknown operator kind");
+  if (kind < GDM_OP_MASS || kind > GDM_OP_ELASTICITY) return fail(GDM_ERR_ARG, "unknown operator kind");
+  if (kind == GDM_OP_ELASTICITY) {
+    if (dim == 1) return fail(GDM_ERR_UNSUPPORTED, "elasticity: dim must be 2 or 3");
+    if (mesh->n_ranks > 1) return fail(GDM_ERR_UNSUPPORTED, "elasticity: single rank only");
+    if (mesh->periodic) return fail(GDM_ERR_UNSUPPORTED, "elasticity: not with periodic constraints");
+    if (n_params < 2 || !params) return fail(GDM_ERR_ARG, "elasticity needs the Lame parameters mu, lambda");
+    if (!(params[0] > 0.0) || !(params[1] >= 0.0) || !std::isfinite(params[0]) || !std::isfinite(params[1]))
+      return fail(GDM_ERR_ARG, "elasticity: mu > 0 and lambda >= 0");
+  }
   for (int d = 0; d < dim; ++d) {
     if (mesh->n_subdivisions[d] < p)
       return fail(GDM_ERR_ARG, "n_subdivisions must be >= fe_degree in every direction");
@@ -1482,6 +1606,10 @@ int gdm_op_create(const gdm_mesh_desc *mesh, int kind, const double *params, int
   if (kind == GDM_OP_ADVECTION || kind == GDM_OP_CONVECTIVE)
     for (int d = 0; d < dim; ++d) op->a[d] = params[d];
   if (kind == GDM_OP_WAVE && n_params >= 1 && params) op->nitsche = params[0];
+  if (kind == GDM_OP_ELASTICITY) {
+    op->el.mu = params[0];
+    op->el.lambda = params[1];
+  }
   // kernel axes: 3D (x, y, z) partition z; 2D (x, y, -) partition y; 1D (-, -, x) partition z
   if (dim == 3) {
     op->kdir[0] = 0; op->kdir[1] = 1; op->kdir[2] = 2; op->part_axis = 2;
@@ -1502,6 +1630,7 @@ int gdm_op_create(const gdm_mesh_desc *mesh, int kind, const double *params, int
   build_faces(op);
   if (mesh->periodic) build_periodic_mass(op);
   if (mesh->n_ranks == 1 && !mesh->periodic) build_load(op);
+  if (kind == GDM_OP_ELASTICITY) build_elasticity(op);
   op->zchunk = choose_zchunk(op);
   hip_check(hipMalloc(&op->dot_partial, sizeof(double) * op->n_dot_partial), "hipMalloc");
   keep(op, op->dot_partial);
@@ -1874,9 +2003,15 @@ const char *kFieldPlanes = "gdm_apply_planes: not with a separable advection fie
 int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const double *bc_values) {
   if (!op) return fail(GDM_ERR_ARG, "op is NULL");
   if (op->layout.n_owned > 0 && (!src_local || !dst_owned)) return fail(GDM_ERR_ARG, "NULL vector");
+  if (op->kind == GDM_OP_ELASTICITY) {
+    if (bc_values) return fail(GDM_ERR_ARG, "gdm_apply: an elasticity operator takes no boundary values");
+    if (src_local == dst_owned) return fail(GDM_ERR_ARG, "gdm_apply: src and dst must be distinct vectors");
+  }
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
-  if (op->field.active) {
+  if (op->kind == GDM_OP_ELASTICITY) {
+    elasticity_apply(op, src_local, dst_owned);
+  } else if (op->field.active) {
     field_apply(op, src_local, dst_owned, bc_values);
   } else if (op->concurrent && !op->mesh.periodic) {
     apply_with_faces(op, op->kind == GDM_OP_MASS, src_local, dst_owned, bc_values);
@@ -1894,6 +2029,7 @@ int gdm_apply_planes(gdm_op *op, const double *src_local, double *dst_owned, int
   if (op->part_axis != 2 && (plane_begin > op->layout.owned_plane_begin || plane_end < op->layout.owned_plane_end))
     return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: plane sub-ranges need a 3D mesh");
   if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: periodic constraints");
+  if (op->kind == GDM_OP_ELASTICITY) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: not for elasticity operators");
   if (op->field.active) return fail(GDM_ERR_UNSUPPORTED, kFieldPlanes);
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
@@ -1908,6 +2044,7 @@ int gdm_apply_planes2(gdm_op *op, const double *src_local, double *dst_owned, in
   if (op->layout.n_owned > 0 && (!src_local || !dst_owned)) return fail(GDM_ERR_ARG, "NULL vector");
   if (op->part_axis != 2) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: plane ranges need a 3D mesh");
   if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: periodic constraints");
+  if (op->kind == GDM_OP_ELASTICITY) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: not for elasticity operators");
   if (op->field.active) return fail(GDM_ERR_UNSUPPORTED, kFieldPlanes);
   // clip both ranges to the owned planes first (a first range in
   // the ghost planes must not drop the second), then test overlap and emptiness
@@ -2579,13 +2716,9 @@ int gdm_add_boundary_fn(gdm_op *op, double *dst_owned, int fn_kind, const double
   GDM_GUARD_END
 }
 
-int gdm_error_norms(gdm_op *op, const double *u_local, int fn_kind, const double *params, int n_params, double t,
-                    double *cell_errors, double *norms_host) {
-  if (!op || !norms_host) return fail(GDM_ERR_ARG, "NULL argument");
-  if (op->layout.n_local > 0 && !u_local) return fail(GDM_ERR_ARG, "NULL u_local");
-  const int need[3] = {1, 1 + op->dim, 9};
-  if (fn_kind < 0 || fn_kind > 2) return fail(GDM_ERR_ARG, "unknown gdm_fn_kind");
-  if (n_params < need[fn_kind] || (n_params > 0 && !params)) return fail(GDM_ERR_ARG, "too few function parameters");
+// gdm_error_norms / gdm_error_norms_grid: fn_kind a gdm_fn_kind with its params, or gdmk::ERR_FN_GRID with exq
+static int error_norms_impl(gdm_op *op, const double *u_local, int fn_kind, const double *params, int n_params,
+                            double t, const double *exq, double *cell_errors, double *norms_host) {
   if (op->p + 1 > 10) return fail(GDM_ERR_UNSUPPORTED, "fe_degree > 9");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
@@ -2632,8 +2765,8 @@ int gdm_error_norms(gdm_op *op, const double *u_local, int fn_kind, const double
   double out[3] = {0.0, 0.0, 0.0};
   if (g.ce[q] > g.cb[q]) {
     double *res = op->err_partial + 3 * op->n_err_partial;
-    hip_check(gdmk_launch_error_norms(g, fn, t, op->err_S, u_local, cell_errors, op->err_partial, op->n_err_partial,
-                                      res, op->stream),
+    hip_check(gdmk_launch_error_norms(g, fn, t, op->err_S, u_local, exq, cell_errors, op->err_partial,
+                                      op->n_err_partial, res, op->stream),
               "error_norms");
     hip_check(hipMemcpyAsync(out, res, sizeof(out), hipMemcpyDeviceToHost, op->stream), "d2h");
     hip_check(hipStreamSynchronize(op->stream), "sync");
@@ -2643,6 +2776,24 @@ int gdm_error_norms(gdm_op *op, const double *u_local, int fn_kind, const double
   norms_host[2] = std::sqrt(out[2]);
   return GDM_OK;
   GDM_GUARD_END
+}
+
+int gdm_error_norms(gdm_op *op, const double *u_local, int fn_kind, const double *params, int n_params, double t,
+                    double *cell_errors, double *norms_host) {
+  if (!op || !norms_host) return fail(GDM_ERR_ARG, "NULL argument");
+  if (op->layout.n_local > 0 && !u_local) return fail(GDM_ERR_ARG, "NULL u_local");
+  const int need[3] = {1, 1 + op->dim, 9};
+  if (fn_kind < 0 || fn_kind > 2) return fail(GDM_ERR_ARG, "unknown gdm_fn_kind");
+  if (n_params < need[fn_kind] || (n_params > 0 && !params)) return fail(GDM_ERR_ARG, "too few function parameters");
+  return error_norms_impl(op, u_local, fn_kind, params, n_params, t, nullptr, cell_errors, norms_host);
+}
+
+int gdm_error_norms_grid(gdm_op *op, const double *u_local, const double *exact_q, double *cell_errors,
+                         double *norms_host) {
+  if (!op || !norms_host) return fail(GDM_ERR_ARG, "NULL argument");
+  if (op->layout.n_local > 0 && !u_local) return fail(GDM_ERR_ARG, "NULL u_local");
+  if (!exact_q) return fail(GDM_ERR_ARG, "NULL exact_q");
+  return error_norms_impl(op, u_local, gdmk::ERR_FN_GRID, nullptr, 0, 0.0, exact_q, cell_errors, norms_host);
 }
 
 }  // extern "C"
@@ -2966,6 +3117,249 @@ int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_own
     hip_check(gdmk_launch_fastdiag_pass(P, src, dst, op->stream), "fastdiag pass");
     src = dst;
   }
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+}  // extern "C"
+
+namespace {
+
+// shared refusals of the elasticity entry points; 0 = ok
+int check_elasticity_op(gdm_op *op, const char *what, bool need_setup) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_ELASTICITY) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": elasticity operators only");
+  if (need_setup && !op->el.built)
+    return fail(GDM_ERR_STATE, std::string(what) + ": call gdm_elasticity_precond_setup first");
+  return GDM_OK;
+}
+
+// z = B^-1 r, component by component: S^T along x, y, z (the last one scales by
+// 1 / sum_d w_cd lambda_d), S along z, y, x, through the two scratch vectors
+void elasticity_precond_launch(gdm_op *op, const double *r, double *z) {
+  const int64_t n = op->layout.n_owned;
+  const int n_axes = op->dim, n_pass = 2 * n_axes;
+  for (int c = 0; c < op->dim; ++c) {
+    const double *src = r + c * n;
+    for (int i = 0; i < n_pass; ++i) {
+      const bool fwd = i < n_axes;
+      const int ax = fwd ? i : n_pass - 1 - i;
+      gdmk::FastdiagPass P{};
+      P.N = op->K[ax];
+      P.Tt = fwd ? op->el.S[ax] : op->el.St[ax];
+      P.K0 = op->K[0];
+      P.K1 = op->K[1];
+      if (ax == 0) {
+        P.row_form = 1;
+        P.cols = 1;
+        P.batch = (int64_t)op->K[1] * op->K[2];
+      } else {
+        P.cols = ax == 1 ? op->K[0] : (int64_t)op->K[0] * op->K[1];
+        P.batch = ax == 1 ? op->K[2] : 1;
+      }
+      if (i == n_axes - 1) {
+        P.scale = 1;
+        P.alpha = 0.0;
+        P.tau = 1.0;
+        P.lam0 = op->el.lam[c][0];
+        P.lam1 = op->el.lam[c][1];
+        P.lam2 = op->el.lam[c][2];
+      }
+      double *dst = i == n_pass - 1 ? z + c * n : op->el.tmp[i & 1];
+      hip_check(gdmk_launch_fastdiag_pass(P, src, dst, op->stream), "fastdiag pass");
+      src = dst;
+    }
+  }
+}
+
+void elasticity_need_invdiag(gdm_op *op) {
+  if (op->el.invdiag) return;
+  std::vector<double> inv = elasticity_diagonal_host(&op->mesh, op->el.mu, op->el.lambda);
+  for (double &v : inv) v = 1.0 / v;
+  op->el.invdiag = keep(op, dev_upload(inv));
+}
+
+}  // namespace
+
+extern "C" {
+
+int gdm_elasticity_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (dim < 2 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 2 or 3");
+  if (tile_x) *tile_x = gdmk::ELAS_TX;
+  if (tile_y) *tile_y = gdmk::ELAS_TY;
+  if (z_chunk) *z_chunk = dim == 3 ? gdmk::ELAS_ZC : 1;
+  return GDM_OK;
+}
+
+int gdm_elasticity_tables_1d(const gdm_mesh_desc *mesh, int axis, double *bands_host, double *S_host,
+                             double *lambda_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  for (int d = 0; d < mesh->dim; ++d)
+    if (mesh->n_subdivisions[d] < 1 || !(mesh->hi[d] > mesh->lo[d])) return fail(GDM_ERR_ARG, "empty box");
+  if ((S_host == nullptr) != (lambda_host == nullptr)) return fail(GDM_ERR_ARG, "S_host and lambda_host go together");
+  GDM_GUARD_BEGIN
+  if (bands_host) {
+    const std::vector<double> t = elasticity_table(elasticity_bands(mesh, axis));
+    std::copy(t.begin(), t.end(), bands_host);
+  }
+  if (S_host) {
+    const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+    std::vector<double> S, lambda;
+    gdm::elasticity_fastdiag_1d(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc, S, lambda);
+    std::copy(S.begin(), S.end(), S_host);
+    std::copy(lambda.begin(), lambda.end(), lambda_host);
+  }
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_elasticity_diagonal(gdm_op *op, double *diag) {
+  if (int rc = check_elasticity_op(op, "gdm_elasticity_diagonal", false)) return rc;
+  if (!diag) return fail(GDM_ERR_ARG, "NULL vector");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const std::vector<double> d = elasticity_diagonal_host(&op->mesh, op->el.mu, op->el.lambda);
+  hip_check(hipMemcpyAsync(diag, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, op->stream), "h2d");
+  hip_check(hipStreamSynchronize(op->stream), "sync");
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_elasticity_precond_setup(gdm_op *op) {
+  if (int rc = check_elasticity_op(op, "gdm_elasticity_precond_setup", false)) return rc;
+  if (op->el.built) return GDM_OK;
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  // everything is uploaded before the handle changes: a failure leaves it as it was
+  gdm_op::Elasticity ne = op->el;
+  std::vector<void *> made;
+  auto up = [&](const std::vector<double> &h) {
+    double *d = dev_upload(h);
+    made.push_back(d);
+    return d;
+  };
+  try {
+    double w[3][3];
+    elasticity_weights(op->el.mu, op->el.lambda, w);
+    for (int d = 0; d < op->dim; ++d) {  // kernel axis d = reference direction d in 2D and 3D
+      const unsigned nc = (unsigned)op->mesh.n_subdivisions[d];
+      std::vector<double> S, lambda;
+      gdm::elasticity_fastdiag_1d(op->p, nc, (op->mesh.hi[d] - op->mesh.lo[d]) / nc, S, lambda);
+      const int n = (int)lambda.size();
+      std::vector<double> St((size_t)n * n);
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
+      ne.S[d] = up(S);
+      ne.St[d] = up(St);
+      for (int c = 0; c < op->dim; ++c) {
+        std::vector<double> wl(lambda);
+        for (double &v : wl) v *= w[c][d];
+        ne.lam[c][d] = up(wl);
+      }
+    }
+    for (int i = 0; i < 2; ++i) {
+      double *t = nullptr;
+      hip_check(hipMalloc(&t, std::max<size_t>((size_t)op->layout.n_owned, 1) * sizeof(double)), "hipMalloc");
+      made.push_back(t);
+      ne.tmp[i] = t;
+    }
+  } catch (...) {
+    for (void *ptr : made) (void)hipFree(ptr);
+    throw;
+  }
+  for (void *ptr : made) op->allocations.push_back(ptr);
+  ne.built = true;
+  op->el = ne;
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_elasticity_precond(gdm_op *op, const double *r, double *z) {
+  if (int rc = check_elasticity_op(op, "gdm_elasticity_precond", true)) return rc;
+  if (!r || !z || r == z) return fail(GDM_ERR_ARG, "gdm_elasticity_precond: r and z are distinct device vectors");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  elasticity_precond_launch(op, r, z);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_elasticity_solve(gdm_op *op, const double *rhs, double *x, int precond, double rel_tol, double abs_tol,
+                         int max_it, int *its_host, double *res_host) {
+  if (int rc = check_elasticity_op(op, "gdm_elasticity_solve", precond == 2)) return rc;
+  if (!rhs || !x || rhs == x) return fail(GDM_ERR_ARG, "rhs and x: distinct device vectors");
+  if (precond < 0 || precond > 2) return fail(GDM_ERR_ARG, "precond: 0 none, 1 Jacobi, 2 block fast diagonalisation");
+  if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const int64_t n = op->layout.n_owned * op->dim;
+  for (double *&v : op->el.cg)
+    if (!v) v = keep(op, dev_upload(std::vector<double>((size_t)std::max<int64_t>(n, 1), 0.0)));
+  if (!op->el.free_mask) op->el.free_mask = keep(op, dev_upload(elasticity_mask_host(op)));
+  if (precond == 1) elasticity_need_invdiag(op);
+  double *r = op->el.cg[0], *p = op->el.cg[1], *Ap = op->el.cg[2], *z = op->el.cg[3], *b = op->el.cg[4];
+  auto dot = [&](const double *u, const double *v) {
+    double s = 0.0;
+    if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
+    return s;
+  };
+  auto precondition = [&](const double *rr, double *zz) {
+    if (precond == 2)
+      elasticity_precond_launch(op, rr, zz);
+    else if (precond == 1)
+      hip_check(gdmk_launch_vmul(n, op->el.invdiag, rr, zz, op->stream), "jacobi");
+    else
+      hip_check(hipMemcpyAsync(zz, rr, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
+  };
+  // the constrained entries of rhs count as 0 and those of x are 0 (the zero
+  // boundary constraints); then SolverCG with ReductionControl(max_it, abs_tol,
+  // rel_tol) on P A P + I - P: r = b - A x
+  hip_check(gdmk_launch_vmul(n, op->el.free_mask, rhs, b, op->stream), "mask");
+  hip_check(gdmk_launch_vmul(n, op->el.free_mask, x, p, op->stream), "mask");
+  hip_check(hipMemcpyAsync(x, p, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
+  elasticity_apply(op, x, r);
+  hip_check(gdmk_launch_axpby(n, 1.0, b, -1.0, r, op->stream), "axpby");
+  double res = std::sqrt(dot(r, r));
+  const double tol = std::max(abs_tol, rel_tol * res);
+  int it = 0;
+  if (res > tol) {
+    precondition(r, z);
+    hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
+    double rz = dot(r, z);
+    while (true) {
+      if (it >= max_it) {
+        if (its_host) *its_host = it;
+        if (res_host) *res_host = res;
+        return fail(GDM_ERR_STATE, "gdm_elasticity_solve: max_it reached (SolverControl::NoConvergence)");
+      }
+      ++it;
+      elasticity_apply(op, p, Ap);
+      const double alpha = rz / dot(p, Ap);
+      hip_check(gdmk_launch_axpby(n, alpha, p, 1.0, x, op->stream), "axpby");
+      hip_check(gdmk_launch_axpby(n, -alpha, Ap, 1.0, r, op->stream), "axpby");
+      res = std::sqrt(dot(r, r));
+      if (res <= tol) break;
+      precondition(r, z);
+      const double rz_new = dot(r, z);
+      hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
+      rz = rz_new;
+    }
+  }
+  if (its_host) *its_host = it;
+  if (res_host) *res_host = res;
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_vec_interleave(gdm_op *op, int n_components, int to_reference, const double *src, double *dst) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (n_components < 1) return fail(GDM_ERR_ARG, "n_components < 1");
+  if (to_reference != 0 && to_reference != 1) return fail(GDM_ERR_ARG, "to_reference must be 0 or 1");
+  if (!src || !dst || src == dst) return fail(GDM_ERR_ARG, "gdm_vec_interleave: src and dst are distinct device vectors");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  hip_check(gdmk_launch_interleave(op->layout.n_owned, n_components, to_reference, src, dst, op->stream), "interleave");
   return GDM_OK;
   GDM_GUARD_END
 }

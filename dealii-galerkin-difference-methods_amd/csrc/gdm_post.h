@@ -22,13 +22,19 @@ struct ErrGeom {
   double xq[10], wq[10];  // QGauss(p+1) on [0, 1]
 };
 
+// BcFn::kind of gdm_error_norms_grid (next to the public gdm_fn_kind values 0..2)
+constexpr int ERR_FN_GRID = 3;
+
 }  // namespace gdmk
 
 extern "C" {
 size_t gdmk_error_norms_lds_bytes(int p, int dim);
 // S: [max(1, p)][p+1][p+1] shape values phi^cat_i(xq_q); out3 (device) =
-// (Linf, L1, L2^2) of the owned cells; partial: 3 * n_partial doubles
+// (Linf, L1, L2^2) of the owned cells; partial: 3 * n_partial doubles.
+// f.kind == gdmk::ERR_FN_GRID: the exact solution is exq, a device array on the
+// tensor Gauss grid of the whole mesh (x fastest, gdm_add_load's fq layout);
+// otherwise exq is not read.
 hipError_t gdmk_launch_error_norms(const gdmk::ErrGeom &g, const gdmk::BcFn &f, double t, const double *S,
-                                   const double *u, double *cell_err, double *partial, int n_partial, double *out3,
-                                   hipStream_t st);
+                                   const double *u, const double *exq, double *cell_err, double *partial,
+                                   int n_partial, double *out3, hipStream_t st);
 }

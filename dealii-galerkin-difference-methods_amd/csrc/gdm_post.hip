@@ -54,8 +54,8 @@ __device__ __forceinline__ double sine_1d(const BcFn &f, int e, double x, double
 //      S[NCAT][N1][N1] | fx[CX][N1] | fy[N1] | fz[N1] | cacc[TPC][CX] ; W = CX + P
 template <int P, int DIM>
 __global__ void __launch_bounds__(NT) error_norms_kernel(ErrGeom g, BcFn f, double t, const double *__restrict__ S,
-                                                         const double *__restrict__ u, double *__restrict__ cell_err,
-                                                         double *__restrict__ partial) {
+                                                         const double *__restrict__ u, const double *__restrict__ exq,
+                                                         double *__restrict__ cell_err, double *__restrict__ partial) {
   constexpr int N1 = P + 1, W = CX + P;
   constexpr int NB1 = DIM > 1 ? N1 : 1, NB2 = DIM > 2 ? N1 : 1;  // = quadrature points per direction
   constexpr int NCAT = P > 1 ? P : 1;
@@ -152,6 +152,11 @@ __global__ void __launch_bounds__(NT) error_norms_kernel(ErrGeom g, BcFn f, doub
           double ex;
           if (f.kind == 2) {
             ex = fx[cl * N1 + qx] * fyz;
+          } else if (f.kind == 3) {
+            // the exact solution sampled on the tensor Gauss grid (gdm_error_norms_grid), x fastest
+            const int64_t Qx = (int64_t)g.ncell[0] * N1, Qy = DIM > 1 ? (int64_t)g.ncell[1] * N1 : 1;
+            const int64_t iy = DIM > 1 ? cy * N1 + qy : 0, iz = DIM > 2 ? cz * N1 + qz : 0;
+            ex = exq[(iz * Qy + iy) * Qx + (int64_t)cx * N1 + qx];
           } else if (f.kind == 1) {
             const double d0 = g.lo[0] + (cx + g.xq[qx]) * g.h[0] - f.prm[1];
             const double d1 = DIM > 1 ? g.lo[1] + (cy + g.xq[qy]) * g.h[1] - f.prm[2] : 0.0;
@@ -249,7 +254,7 @@ extern "C" size_t gdmk_error_norms_lds_bytes(int p, int dim) {
 namespace {
 template <int P, int DIM>
 hipError_t launch_err(const gdmk::ErrGeom &g, const gdmk::BcFn &f, double t, const double *S, const double *u,
-                      double *cell_err, double *partial, int n_partial, hipStream_t st) {
+                      const double *exq, double *cell_err, double *partial, int n_partial, hipStream_t st) {
   const size_t lds = gdmk_error_norms_lds_bytes(P, DIM);
   if (lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gdmk::error_norms_kernel<P, DIM>),
@@ -257,34 +262,34 @@ hipError_t launch_err(const gdmk::ErrGeom &g, const gdmk::BcFn &f, double t, con
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL((gdmk::error_norms_kernel<P, DIM>), dim3((unsigned)n_partial), dim3(gdmk::NT), lds, st, g, f, t,
-                     S, u, cell_err, partial);
+                     S, u, exq, cell_err, partial);
   return hipSuccess;
 }
 template <int P>
 hipError_t launch_err_dim(const gdmk::ErrGeom &g, const gdmk::BcFn &f, double t, const double *S, const double *u,
-                          double *cell_err, double *partial, int n_partial, hipStream_t st) {
+                          const double *exq, double *cell_err, double *partial, int n_partial, hipStream_t st) {
   switch (g.dim) {
-    case 1: return launch_err<P, 1>(g, f, t, S, u, cell_err, partial, n_partial, st);
-    case 2: return launch_err<P, 2>(g, f, t, S, u, cell_err, partial, n_partial, st);
-    default: return launch_err<P, 3>(g, f, t, S, u, cell_err, partial, n_partial, st);
+    case 1: return launch_err<P, 1>(g, f, t, S, u, exq, cell_err, partial, n_partial, st);
+    case 2: return launch_err<P, 2>(g, f, t, S, u, exq, cell_err, partial, n_partial, st);
+    default: return launch_err<P, 3>(g, f, t, S, u, exq, cell_err, partial, n_partial, st);
   }
 }
 }  // namespace
 
 extern "C" hipError_t gdmk_launch_error_norms(const gdmk::ErrGeom &g, const gdmk::BcFn &f, double t,
-                                             const double *S, const double *u, double *cell_err, double *partial,
-                                             int n_partial, double *out3, hipStream_t st) {
+                                             const double *S, const double *u, const double *exq, double *cell_err,
+                                             double *partial, int n_partial, double *out3, hipStream_t st) {
   hipError_t e;
   switch (g.p) {
-    case 1: e = launch_err_dim<1>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 2: e = launch_err_dim<2>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 3: e = launch_err_dim<3>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 4: e = launch_err_dim<4>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 5: e = launch_err_dim<5>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 6: e = launch_err_dim<6>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 7: e = launch_err_dim<7>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 8: e = launch_err_dim<8>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
-    case 9: e = launch_err_dim<9>(g, f, t, S, u, cell_err, partial, n_partial, st); break;
+    case 1: e = launch_err_dim<1>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 2: e = launch_err_dim<2>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 3: e = launch_err_dim<3>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 4: e = launch_err_dim<4>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 5: e = launch_err_dim<5>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 6: e = launch_err_dim<6>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 7: e = launch_err_dim<7>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 8: e = launch_err_dim<8>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
+    case 9: e = launch_err_dim<9>(g, f, t, S, u, exq, cell_err, partial, n_partial, st); break;
     default: return hipErrorInvalidValue;
   }
   if (e != hipSuccess) return e;

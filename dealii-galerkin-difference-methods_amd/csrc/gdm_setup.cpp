@@ -390,10 +390,20 @@ void symmetric_eigen(int n, std::vector<double> &a, std::vector<double> &d) {
 void fastdiag_1d(int p, unsigned n_cells, double h, double nitsche_over_hmin, std::vector<double> &S,
                  std::vector<double> &lambda) {
   const Matrices1D m = assemble_1d(p, n_cells, h);
-  const Band B = wave_band_1d(p, n_cells, h, nitsche_over_hmin, m);
-  const int n = m.M.n, hb = m.M.hb, wl = hb + 1;
+  Band B = wave_band_1d(p, n_cells, h, nitsche_over_hmin, m);
+  for (double &v : B.a) v = -v;
+  fastdiag_pencil(B, m.M, S, lambda);
+}
+
+void fastdiag_pencil(const Band &A, const Band &M, std::vector<double> &S, std::vector<double> &lambda) {
+  const int n = M.n, hb = M.hb, wl = hb + 1;
+  if (n == 0) {
+    S.clear();
+    lambda.clear();
+    return;
+  }
   std::vector<double> lrow, invd;
-  cholesky_band(m.M, lrow, invd);
+  cholesky_band(M, lrow, invd);
   auto R = [&](int i, int j) { return lrow[(size_t)i * wl + (j - i + hb)]; };  // i - hb <= j <= i
   // forward substitution R y = x in place, x a contiguous vector
   auto forward = [&](double *x) {
@@ -406,7 +416,7 @@ void fastdiag_1d(int p, unsigned n_cells, double h, double nitsche_over_hmin, st
   // c[j * n + i]: column j of A, then of R^-1 A; transposed, again: R^-1 (R^-1 A)^T = R^-1 A R^-T
   std::vector<double> c((size_t)n * n, 0.0), t((size_t)n * n);
   for (int j = 0; j < n; ++j) {
-    for (int i = std::max(0, j - hb); i <= std::min(n - 1, j + hb); ++i) c[(size_t)j * n + i] = -B(i, j);
+    for (int i = std::max(0, j - hb); i <= std::min(n - 1, j + hb); ++i) c[(size_t)j * n + i] = A(i, j);
     forward(&c[(size_t)j * n]);
   }
   for (int j = 0; j < n; ++j)
@@ -432,6 +442,44 @@ void fastdiag_1d(int p, unsigned n_cells, double h, double nitsche_over_hmin, st
       if (std::fabs(x[i]) > std::fabs(x[big])) big = i;
     const double sg = x[big] < 0.0 ? -1.0 : 1.0;
     for (int i = 0; i < n; ++i) S[(size_t)i * n + j] = sg * x[i];
+  }
+}
+
+ElasticityBands1D elasticity_bands_1d(int p, unsigned n_cells, double h) {
+  const Matrices1D m = assemble_1d(p, n_cells, h);
+  const int n = m.M.n, last = n - 1;
+  ElasticityBands1D b;
+  b.M = Band(n, p);
+  b.C = Band(n, p);
+  b.Ct = Band(n, p);
+  b.L = Band(n, p);
+  // P A P: rows and columns 0 and n - 1 stay zero
+  for (int i = 1; i < last; ++i)
+    for (int j = std::max(1, i - p); j <= std::min(last - 1, i + p); ++j) {
+      b.M(i, j) = m.M(i, j);
+      b.C(i, j) = m.C(i, j);
+      b.Ct(i, j) = m.C(j, i);
+      b.L(i, j) = m.L(i, j);
+    }
+  return b;
+}
+
+void elasticity_fastdiag_1d(int p, unsigned n_cells, double h, std::vector<double> &S, std::vector<double> &lambda) {
+  const ElasticityBands1D b = elasticity_bands_1d(p, n_cells, h);
+  const int n = b.M.n, ni = std::max(0, n - 2);
+  Band Mi(ni, p), Li(ni, p);
+  for (int i = 0; i < ni; ++i)
+    for (int j = std::max(0, i - p); j <= std::min(ni - 1, i + p); ++j) {
+      Mi(i, j) = b.M(i + 1, j + 1);
+      Li(i, j) = b.L(i + 1, j + 1);
+    }
+  std::vector<double> Si, li;
+  fastdiag_pencil(Li, Mi, Si, li);
+  S.assign((size_t)n * n, 0.0);
+  lambda.assign((size_t)n, 1.0);
+  for (int i = 0; i < ni; ++i) {
+    lambda[i + 1] = li[i];
+    for (int j = 0; j < ni; ++j) S[(size_t)(i + 1) * n + (j + 1)] = Si[(size_t)i * ni + j];
   }
 }
 

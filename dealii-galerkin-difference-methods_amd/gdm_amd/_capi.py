@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GDM_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libgd
 HEADER = os.path.join(os.path.dirname(PKG_ROOT), "include", "gdm_hip.h")
 
 GDM_OK = 0
-GDM_OP_MASS, GDM_OP_ADVECTION, GDM_OP_WAVE, GDM_OP_CONVECTIVE = 0, 1, 2, 3
+GDM_OP_MASS, GDM_OP_ADVECTION, GDM_OP_WAVE, GDM_OP_CONVECTIVE, GDM_OP_ELASTICITY = 0, 1, 2, 3, 4
 
 
 class GdmError(RuntimeError):
@@ -173,6 +173,15 @@ def load():
         "gdm_system_solve_setup": [P],
         "gdm_system_solve": [P, d, d, P, P],
         "gdm_fastdiag_transform": [P, i32, i32, P, P],
+        "gdm_elasticity_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                ctypes.POINTER(ctypes.c_int)],
+        "gdm_elasticity_tables_1d": [ctypes.POINTER(MeshDesc), i32, P, P, P],
+        "gdm_elasticity_diagonal": [P, P],
+        "gdm_elasticity_precond_setup": [P],
+        "gdm_elasticity_precond": [P, P, P],
+        "gdm_elasticity_solve": [P, P, P, i32, d, d, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
+        "gdm_vec_interleave": [P, i32, i32, P, P],
+        "gdm_error_norms_grid": [P, P, P, P, P],
         "gdm_mass_spike_eps": [P, P],
         "gdm_mass_solve_slab": [P, P, P],
         "gdm_mass_solve_interface": [P, P],
@@ -350,6 +359,29 @@ def fastdiag_tables(mesh, nitsche, axis):
     check(load().gdm_fastdiag_tables(ctypes.byref(mesh), float(nitsche), int(axis), S.ctypes.data_as(ctypes.c_void_p),
                                      lam.ctypes.data_as(ctypes.c_void_p)), "gdm_fastdiag_tables")
     return S, lam
+
+
+def elasticity_tile(fe_degree, dim=3):
+    """(tile_x, tile_y, z_chunk) of the elasticity kernel, kernel axes (gdm_elasticity_tile)"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_elasticity_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_elasticity_tile")
+    return tuple(v.value for v in t)
+
+
+def elasticity_tables_1d(mesh, axis):
+    """(bands [4, N, 2p+1], S [N, N], lambda [N]) of direction `axis`: the
+    Dirichlet-reduced M, C, C^T, L and the embedded interior eigenpairs of
+    (L, M).  Pure host, no GPU (gdm_elasticity_tables_1d)."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("elasticity_tables_1d: axis outside [0, dim)")
+    n = mesh.n_subdivisions[axis] + 1
+    bands, S, lam = np.zeros((4, n, 2 * mesh.fe_degree + 1)), np.zeros((n, n)), np.zeros(n)
+    check(load().gdm_elasticity_tables_1d(ctypes.byref(mesh), int(axis), bands.ctypes.data_as(ctypes.c_void_p),
+                                          S.ctypes.data_as(ctypes.c_void_p), lam.ctypes.data_as(ctypes.c_void_p)),
+          "gdm_elasticity_tables_1d")
+    return bands, S, lam
 
 
 def load_tile(fe_degree, dim=3):

@@ -1,7 +1,7 @@
 """Device operator handle over the C ABI (include/gdm_hip.h).
 
 `GdmOperator` owns one `gdm_op`: the uncut structured-mesh GDM operator of
-one rank (mass, advection, wave or convective) with its slab layout.  Vectors
+one rank (mass, advection, wave, convective or elasticity) with its slab layout.  Vectors
 are torch CUDA tensors (fp64); torch is only the allocator / stream provider.
 """
 import ctypes
@@ -16,7 +16,10 @@ KINDS = {
     "advection": _capi.GDM_OP_ADVECTION,
     "wave": _capi.GDM_OP_WAVE,
     "convective": _capi.GDM_OP_CONVECTIVE,
+    "elasticity": _capi.GDM_OP_ELASTICITY,
 }
+
+PRECONDS = {"none": 0, "jacobi": 1, "fastdiag": 2}
 
 
 def _ptr(t):
@@ -58,6 +61,8 @@ class GdmOperator:
         self.mesh = m
         self.dim, self.p = dim, fe_degree
         self.kind = KINDS[kind] if isinstance(kind, str) else kind
+        # elasticity: apply() acts on component-major vectors [u_0 | u_1 | (u_2)] of dim blocks
+        self.n_components = dim if self.kind == _capi.GDM_OP_ELASTICITY else 1
         self.device = device
         self._params = tuple(float(v) for v in params)
         arr = (ctypes.c_double * max(1, len(params)))(*params) if len(params) else None
@@ -110,15 +115,17 @@ class GdmOperator:
         n = self.n_local if local else self.n_owned
         return self._torch.zeros(n, dtype=self._torch.float64, device="cuda:%d" % self.device)
 
-    def _check_sizes(self, src_local, dst_owned):
-        if src_local is not None and src_local.numel() != self.n_local:
-            raise GdmError("src has %d entries, local layout needs %d" % (src_local.numel(), self.n_local))
-        if dst_owned is not None and dst_owned.numel() != self.n_owned:
-            raise GdmError("dst has %d entries, owned layout needs %d" % (dst_owned.numel(), self.n_owned))
+    def _check_sizes(self, src_local, dst_owned, n_components=1):
+        if src_local is not None and src_local.numel() != self.n_local * n_components:
+            raise GdmError("src has %d entries, local layout needs %d" % (src_local.numel(),
+                                                                          self.n_local * n_components))
+        if dst_owned is not None and dst_owned.numel() != self.n_owned * n_components:
+            raise GdmError("dst has %d entries, owned layout needs %d" % (dst_owned.numel(),
+                                                                          self.n_owned * n_components))
 
     # -- operator applications -------------------------------------------------
     def apply(self, src_local, dst_owned, bc_values=None):
-        self._check_sizes(src_local, dst_owned)
+        self._check_sizes(src_local, dst_owned, self.n_components)
         if bc_values is not None and bc_values.numel() != self.n_bc_points:
             raise GdmError("bc_values has %d entries, expected %d" % (bc_values.numel(), self.n_bc_points))
         check(self.lib.gdm_apply(self.h, _ptr(src_local), _ptr(dst_owned), _ptr(bc_values)), "gdm_apply")
@@ -385,6 +392,92 @@ class GdmOperator:
         check(self.lib.gdm_fastdiag_transform(self.h, int(axis), int(transpose), _ptr(src_owned), _ptr(dst_owned)),
               "gdm_fastdiag_transform")
         return dst_owned
+
+    # -- linear elasticity (kind "elasticity": component-major vectors) -----------
+    def new_vector_field(self):
+        """a zero vector of n_components blocks [u_0 | u_1 | (u_2)]"""
+        return self._torch.zeros(self.n_components * self.n_owned, dtype=self._torch.float64,
+                                 device="cuda:%d" % self.device)
+
+    def component(self, v, c):
+        """the view of component c of a component-major vector"""
+        return v[c * self.n_owned:(c + 1) * self.n_owned]
+
+    def elasticity_tile(self):
+        """(tile_x, tile_y, z_chunk) of the elasticity kernel, kernel axes"""
+        return _capi.elasticity_tile(self.p, self.dim)
+
+    def elasticity_tables_1d(self, axis):
+        """(bands, S, lambda) of direction `axis` on the host (gdm_elasticity_tables_1d)"""
+        return _capi.elasticity_tables_1d(self.mesh, axis)
+
+    def elasticity_diagonal(self, diag=None):
+        """the diagonal of P A P + I - P (gdm_elasticity_diagonal)"""
+        if diag is None:
+            diag = self.new_vector_field()
+        self._check_sizes(None, diag, self.n_components)
+        check(self.lib.gdm_elasticity_diagonal(self.h, _ptr(diag)), "gdm_elasticity_diagonal")
+        return diag
+
+    def elasticity_precond_setup(self):
+        """Build and upload the tables of the block fast-diagonalisation
+        preconditioner (gdm_elasticity_precond_setup; idempotent)"""
+        check(self.lib.gdm_elasticity_precond_setup(self.h), "gdm_elasticity_precond_setup")
+
+    def elasticity_precond(self, r, z=None):
+        """z = B^-1 r, B the block diagonal of the operator (gdm_elasticity_precond)"""
+        if z is None:
+            z = self.new_vector_field()
+        self._check_sizes(None, r, self.n_components)
+        self._check_sizes(None, z, self.n_components)
+        check(self.lib.gdm_elasticity_precond(self.h, _ptr(r), _ptr(z)), "gdm_elasticity_precond")
+        return z
+
+    def elasticity_solve(self, rhs, x, precond="fastdiag", rel_tol=1e-8, abs_tol=1e-10, max_it=1000):
+        """Preconditioned CG on P A P + I - P from the initial guess x
+        (gdm_elasticity_solve): returns (iterations, residual).  precond:
+        "none", "jacobi" or "fastdiag" (set up on first use)."""
+        self._check_sizes(None, rhs, self.n_components)
+        self._check_sizes(None, x, self.n_components)
+        pc = PRECONDS[precond] if isinstance(precond, str) else int(precond)
+        if pc == 2 and isinstance(precond, str):
+            self.elasticity_precond_setup()
+        its, res = ctypes.c_int(0), ctypes.c_double(0.0)
+        check(self.lib.gdm_elasticity_solve(self.h, _ptr(rhs), _ptr(x), pc, float(rel_tol), float(abs_tol),
+                                            int(max_it), ctypes.byref(its), ctypes.byref(res)),
+              "gdm_elasticity_solve")
+        return its.value, res.value
+
+    def interleave(self, src, dst=None, n_components=None, to_reference=True):
+        """component-major -> the reference's vertex * n_components + component
+        numbering (to_reference) or back (gdm_vec_interleave)"""
+        nc = self.n_components if n_components is None else int(n_components)
+        if dst is None:
+            dst = self._torch.empty_like(src)
+        self._check_sizes(None, src, nc)
+        self._check_sizes(None, dst, nc)
+        check(self.lib.gdm_vec_interleave(self.h, nc, int(bool(to_reference)), _ptr(src), _ptr(dst)),
+              "gdm_vec_interleave")
+        return dst
+
+    def error_norms_grid(self, u_local, exact_q, cell_errors=None):
+        """error_norms against an exact solution sampled on the tensor Gauss
+        grid (device array in add_load's fq layout; gdm_error_norms_grid)"""
+        if u_local.numel() != self.n_local:
+            raise GdmError("error_norms_grid: u has %d entries, expected n_local %d" % (u_local.numel(),
+                                                                                        self.n_local))
+        nq = 1
+        for d in range(self.dim):
+            nq *= self.mesh.n_subdivisions[d] * (self.p + 1)
+        if exact_q.numel() != nq:
+            raise GdmError("error_norms_grid: exact_q has %d entries, the quadrature grid %d" % (exact_q.numel(), nq))
+        if cell_errors is not None and cell_errors.numel() != self.n_owned_cells:
+            raise GdmError("error_norms_grid: cell_errors has %d entries, expected %d" % (cell_errors.numel(),
+                                                                                          self.n_owned_cells))
+        out = (ctypes.c_double * 3)()
+        check(self.lib.gdm_error_norms_grid(self.h, _ptr(u_local), _ptr(exact_q), _ptr(cell_errors), out),
+              "gdm_error_norms_grid")
+        return tuple(out)
 
     def mass_solve_slab(self, rhs_owned, x_owned):
         """Distributed exact mass inverse, step 1: the slab-local solve

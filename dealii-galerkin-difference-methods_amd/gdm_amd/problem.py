@@ -208,6 +208,37 @@ def solve_poisson(op, forcing=None, dirichlet=None, t=0.0):
     return op.system_solve(0.0, 1.0, rhs, prob.u)
 
 
+def solve_elasticity(op, f_components, exact=None, precond="fastdiag", rel_tol=1e-8, abs_tol=1e-10, max_it=1000):
+    """tests/elasticity_01_gdm.cc on the device: the right-hand side (v_c, f_c)
+    per component through add_load, preconditioned CG from a zero start on the
+    elasticity operator `op`, and, when `exact` is given, the L2 error
+    sqrt(sum_c e_c^2) through error_norms_grid.  f_components / exact: one
+    array per component on the tensor Gauss grid (op.quadrature_points(), x
+    fastest; numpy or device).  Returns (x, iterations) or (x, iterations,
+    error), x component-major on the device."""
+    import numpy as np
+    import torch
+
+    def dev(a):
+        if isinstance(a, torch.Tensor):
+            return a.reshape(-1)
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)).cuda(op.device)
+
+    if len(f_components) != op.n_components:
+        raise GdmError("solve_elasticity: %d right-hand sides for %d components" % (len(f_components),
+                                                                                 op.n_components))
+    rhs, x = op.new_vector_field(), op.new_vector_field()
+    for c, f in enumerate(f_components):
+        op.add_load(dev(f), op.component(rhs, c))
+    its, _ = op.elasticity_solve(rhs, x, precond, rel_tol, abs_tol, max_it)
+    if exact is None:
+        return x, its
+    err2 = 0.0
+    for c, e in enumerate(exact):
+        err2 += op.error_norms_grid(op.component(x, c), dev(e))[2] ** 2
+    return x, its, float(np.sqrt(err2))
+
+
 class AdvectionProblem:
     """advection problem.h:31-102 on one rank with a built-in boundary
     function (gdm_fn_kind) for g and dg/dt."""

@@ -73,7 +73,9 @@ enum gdm_op_kind {
   GDM_OP_MASS = 0,       /* (v, u)                                  mass.h:144-156   */
   GDM_OP_ADVECTION = 1,  /* (a u, grad v) - <(a.n) u_up, v>_box     stiffness.h:345-532 */
   GDM_OP_WAVE = 2,       /* -(grad v, grad u) [+ Nitsche on the box] wave/stiffness.h:151-330 */
-  GDM_OP_CONVECTIVE = 3  /* -(a . grad u, v)  prototypes/advection_01_gdm.cc:164-206 */
+  GDM_OP_CONVECTIVE = 3, /* -(a . grad u, v)  prototypes/advection_01_gdm.cc:164-206 */
+  GDM_OP_ELASTICITY = 4  /* 2 mu (eps(u), eps(v)) + lambda (div u, div v), zero boundary
+                            constraints            tests/elasticity_01_gdm.cc:143-184 */
 };
 
 typedef struct gdm_op gdm_op;
@@ -147,6 +149,8 @@ typedef struct {
  *   GDM_OP_MASS        : none
  *   GDM_OP_ADVECTION   : a_x, a_y, a_z               (constant field, see below)
  *   GDM_OP_CONVECTIVE  : a_x, a_y, a_z
+ *   GDM_OP_ELASTICITY  : mu, lambda                  (mu > 0, lambda >= 0; see "Linear
+ *                                                     elasticity" below)
  *   The reference evaluates advection->value(x_q, d) at every quadrature point
  *   (advection/stiffness.h:395-406, 443, 510).  The params give a CONSTANT
  *   field, which is what every reference preset uses (ConstantFunction,
@@ -593,6 +597,103 @@ int gdm_fastdiag_tables(const gdm_mesh_desc *mesh, double nitsche, int axis, dou
 int gdm_system_solve_setup(gdm_op *op);
 int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned);
 int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *src_owned, double *dst_owned);
+
+/* ------------------------------------------------------------------------
+ * Linear elasticity on uncut boxes (added within ABI 18: new entry points and
+ * one new operator kind only, the version number is unchanged).  The matrix of
+ * tests/elasticity_01_gdm.cc:143-184,
+ *   a(u, v) = 2 mu (eps(u), eps(v)) + lambda (div u, div v)
+ * (the reference has mu = 1, lambda = 0), with the constraints of
+ * System::make_zero_boundary_constraints (system.h:466-498): every component
+ * of every vertex on a box face is constrained to zero.  The operator is
+ * P A P + I - P, P the mask of the free DoFs; the constrained rows carry a unit
+ * diagonal (deal.II puts another positive number there, which changes neither
+ * the CG iterates nor the iteration count while the right-hand side is zero on
+ * those rows).
+ *
+ * Vectors are component-major: u = [u_0 | u_1 | (u_2)], dim blocks of n_dofs
+ * entries, each block a scalar vector in the operator's layout, so every scalar
+ * entry point (gdm_mass_apply, gdm_add_load, gdm_error_norms_grid, ...) works on
+ * one component through a pointer offset.  The reference numbers DoFs vertex *
+ * n_components + component (system.h:242-244): gdm_vec_interleave converts.
+ *
+ *   gdm_op_create(GDM_OP_ELASTICITY, {mu, lambda})
+ *                        dim 2 or 3, single rank, non-periodic
+ *                        (GDM_ERR_UNSUPPORTED otherwise); mu > 0, lambda >= 0
+ *                        (GDM_ERR_ARG).
+ *   gdm_apply            dst = (P A P + I - P) src on vectors of dim * n_dofs
+ *                        entries, one launch for all components
+ *                        (csrc/gdm_elasticity.hip: SparseMatrix::vmult of
+ *                        elasticity_01_gdm.cc:184).  bc_values must be NULL and
+ *                        src != dst (GDM_ERR_ARG).  No allocation; bitwise
+ *                        repeatable.
+ *   gdm_elasticity_tile  pure host: the (x, y) node tile and the z chunk of
+ *                        node planes of the kernel (z_chunk = 1 in 2D).
+ *   gdm_elasticity_tables_1d
+ *                        pure host: the tables of direction `axis`, N =
+ *                        n_subdivisions[axis] + 1.  bands_host [4][N][2p+1]:
+ *                        the Dirichlet-reduced M, C, C^T, L (C_ij = int phi_i'
+ *                        phi_j), entry [f][i][k] = A_f(i, i - p + k), rows and
+ *                        columns 0 and N - 1 zero.  S_host (row-major N x N),
+ *                        lambda_host (N): the generalised eigenpairs of the
+ *                        interior (N-2) x (N-2) pencil (L, M), S^T M S = I,
+ *                        embedded with zero rows / columns 0 and N - 1 of S and
+ *                        lambda = 1 there.  Any of the outputs may be NULL
+ *                        (S_host and lambda_host together).
+ *   gdm_elasticity_diagonal
+ *                        diag (device, dim * n_dofs) = the diagonal of
+ *                        P A P + I - P: PreconditionJacobi::initialize of
+ *                        elasticity_01_gdm.cc:178-179.  Synchronises.
+ *   gdm_elasticity_precond_setup
+ *                        builds and uploads the tables of the block
+ *                        preconditioner and two scratch vectors; idempotent.
+ *                        The only call of the preconditioner that allocates or
+ *                        synchronises.
+ *   gdm_elasticity_precond
+ *                        z = B^-1 r on the free DoFs, 0 on the constrained ones,
+ *                        B = blockdiag_c(P A_cc P + I - P): by Korn's inequality
+ *                        spectrally equivalent to the operator, inverted exactly
+ *                        by fast diagonalisation, B_cc^-1 = (S (x) S (x) S)
+ *                        diag(1 / sum_d w_cd lambda_d) (S (x) S (x) S)^T with w_cd
+ *                        = 2 mu + lambda (d = c), mu otherwise (the passes of
+ *                        gdm_system_solve).  r != z.  No allocation, no host
+ *                        synchronisation: capturable in a hipGraph.
+ *                        GDM_ERR_STATE before setup.
+ *   gdm_elasticity_solve SolverCG with ReductionControl(max_it, abs_tol,
+ *                        rel_tol) (elasticity_01_gdm.cc:181-184), conventions of
+ *                        gdm_mass_solve_cg: x is the initial guess, *its_host =
+ *                        last_step, *res_host = the final residual norm,
+ *                        GDM_ERR_STATE when max_it is reached.  precond: 0 none,
+ *                        1 Jacobi (the reference's), 2 the block fast
+ *                        diagonalisation (GDM_ERR_STATE before
+ *                        gdm_elasticity_precond_setup).  Entries of rhs on
+ *                        constrained DoFs count as 0 and those of x are set to
+ *                        0.  The iteration count of precond 2 does not grow
+ *                        with the mesh (a dozen at lambda = 0, where Jacobi
+ *                        needs hundreds); it grows with lambda / mu towards the
+ *                        incompressible limit (69 at lambda = 50 mu, 2D p = 3,
+ *                        n = 40).  Allocates work vectors on the first call.
+ *   gdm_vec_interleave   to_reference 1: dst[v * n_components + c] = src[c *
+ *                        n_dofs + v] (component-major -> the reference's
+ *                        numbering); 0: the inverse.  src != dst.  Any kind.
+ *   gdm_error_norms_grid gdm_error_norms with the exact solution given as a
+ *                        DEVICE array on the tensor Gauss grid, in the layout
+ *                        of gdm_add_load's fq (integrate_difference against a
+ *                        function that is not built in, elasticity_01_gdm.cc:
+ *                        186-198; one call per component, L2 = sqrt(sum_c
+ *                        L2_c^2)).  Single rank.  Any kind.
+ * ---------------------------------------------------------------------- */
+int gdm_elasticity_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
+int gdm_elasticity_tables_1d(const gdm_mesh_desc *mesh, int axis, double *bands_host, double *S_host,
+                             double *lambda_host);
+int gdm_elasticity_diagonal(gdm_op *op, double *diag);
+int gdm_elasticity_precond_setup(gdm_op *op);
+int gdm_elasticity_precond(gdm_op *op, const double *r, double *z);
+int gdm_elasticity_solve(gdm_op *op, const double *rhs, double *x, int precond, double rel_tol, double abs_tol,
+                         int max_it, int *its_host, double *res_host);
+int gdm_vec_interleave(gdm_op *op, int n_components, int to_reference, const double *src, double *dst);
+int gdm_error_norms_grid(gdm_op *op, const double *u_local, const double *exact_q, double *cell_errors,
+                         double *norms_host);
 
 /* memory helpers for callers without their own device allocator */
 int gdm_malloc(gdm_op *op, size_t bytes, void **ptr);
