@@ -181,6 +181,8 @@ struct gdm_op {
   unsigned long long *tail_counter = nullptr;
   double *mass_tmp = nullptr;  // ping-pong vector of the segmented mass passes (small meshes)
   int64_t mass_tmp_size = 0;
+  int mass_seg_waves = -1;      // gdm_op_set_mass_seg_waves (-1: gdmk_mass3_seg_waves())
+  gdm_mass_path mass_path = {};  // what the last mass_solve_passes launched (gdm_op_mass_path)
   int64_t face_tmp_size = 0;
   double *dot_partial = nullptr, *dot_out = nullptr;
   int n_dot_partial = 1024;
@@ -1487,10 +1489,24 @@ bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, con
     return v3 && t.l3 && span_ok && (q.dir_kind == 1 || (q.len % 2 == 0 && aligned));
   };
   const int np = (int)passes.size();
+  const int seg_waves = op->mass_seg_waves >= 0 ? op->mass_seg_waves : gdmk_mass3_seg_waves();
+  gdm_mass_path &path = op->mass_path;
+  path = gdm_mass_path{};
+  path.n_passes = np;
+  // pass i as launched: v2, or v3 with the launcher's own segment count
+  auto record = [&](int i, const Pass &q, bool is_v3, bool allow_segments, const double *src, const double *dst) {
+    path.pass[i].axis = q.ax;
+    path.pass[i].v3 = is_v3 ? 1 : 0;
+    path.pass[i].segments = is_v3 ? gdmk::gdmk_mass3_segments(gdmk_mass3_chunk(op->p), (int)q.len, q.n_lines,
+                                                              allow_segments, src == dst, gdmk_mass3_seg_waves(),
+                                                              nullptr)
+                                  : 1;
+    path.pass[i].in_place = src == dst ? 1 : 0;
+  };
   bool seg[3] = {false, false, false}, segmented = false;
   for (int i = 0; i < np; ++i) {
     const Pass &q = passes[(size_t)i];
-    seg[i] = v3 && tab[q.ax].l3 && (q.n_lines + 63) / 64 < gdmk_mass3_seg_waves();
+    seg[i] = v3 && tab[q.ax].l3 && (q.n_lines + 63) / 64 < seg_waves;
     segmented = segmented || seg[i];
   }
   double *tmp = nullptr;
@@ -1519,9 +1535,14 @@ bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, con
     if (rk && i == np - 1 && !segmented && !part && q.dir_kind == 0 && use_v3(q, in, in)) {
       const hipError_t e = gdmk_launch_mass3_rk(op->p, in, (int)q.len, q.n_lines, t.l3, t.u3, t.d3, t.cst.data(),
                                                 t.row_lo, t.row_hi, *rk, op->stream);
-      if (e == hipSuccess) return true;
+      if (e == hipSuccess) {
+        record(i, q, true, false, in, nullptr);
+        path.rk_mode = rk->Y ? (rk->acc_in == rk->y ? 3 : 2) : 1;
+        return true;
+      }
       if (e != hipErrorNotSupported) hip_check(e, "mass x + rk update");
     }
+    record(i, q, use_v3(q, in, out), seg[i], in, out);
     if (use_v3(q, in, out))
       hip_check(gdmk_launch_mass3(op->p, q.dir_kind, in, out, (int)q.len, q.stride, q.n_lines, q.A, q.B, t.l3, t.u3,
                                   t.d3, t.cst.data(), t.row_lo, t.row_hi, seg[i] ? 1 : 0, op->stream),
@@ -2220,6 +2241,20 @@ int gdm_mass_solve_rk(gdm_op *op, double *rhs_owned, double beta, const double *
               "rk_update");
   return GDM_OK;
   GDM_GUARD_END
+}
+
+int gdm_op_set_mass_seg_waves(gdm_op *op, int waves) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (waves < -1 || waves > gdmk_mass3_seg_waves())
+    return fail(GDM_ERR_ARG, "gdm_op_set_mass_seg_waves: waves outside [-1, default threshold]");
+  op->mass_seg_waves = waves;
+  return GDM_OK;
+}
+
+int gdm_op_mass_path(const gdm_op *op, gdm_mass_path *out) {
+  if (!op || !out) return fail(GDM_ERR_ARG, "NULL argument");
+  *out = op->mass_path;
+  return GDM_OK;
 }
 
 int gdm_mass_solve_periodic(gdm_op *op, const double *rhs_owned, double *x_owned) {

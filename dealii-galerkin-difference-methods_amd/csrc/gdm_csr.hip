@@ -561,6 +561,27 @@ int gdm_csr_set_stream(gdm_csr *A, void *hip_stream) {
   return GDM_OK;
 }
 
+int gdm_csr_set_lanes(gdm_csr *A, int K) {
+  if (!A) return fail(GDM_ERR_ARG, "matrix is NULL");
+  if (K == 0) {
+    A->mode = A->n_rows > 0 ? 1 : 0;  // an empty matrix has no row blocks (and launches nothing)
+    A->K = pick_lanes(A->n_rows, A->nnz);
+    return GDM_OK;
+  }
+  if (K != 2 && K != 4 && K != 8 && K != 16 && K != 32 && K != 64)
+    return fail(GDM_ERR_ARG, "lanes must be 0 (row-block kernel) or one of 2, 4, 8, 16, 32, 64");
+  A->mode = 0;
+  A->K = K;
+  return GDM_OK;
+}
+
+int gdm_csr_kernel(const gdm_csr *A, int *mode, int *lanes) {
+  if (!A) return fail(GDM_ERR_ARG, "matrix is NULL");
+  if (mode) *mode = A->mode;
+  if (lanes) *lanes = A->mode == 1 ? 0 : A->K;
+  return GDM_OK;
+}
+
 int gdm_csr_download(const gdm_csr *A, int64_t *row_ptr_host, uint32_t *cols_host, double *vals_host) {
   if (!A || !row_ptr_host || (A->nnz > 0 && (!cols_host || !vals_host))) return fail(GDM_ERR_ARG, "NULL argument");
   GDM_GUARD_BEGIN

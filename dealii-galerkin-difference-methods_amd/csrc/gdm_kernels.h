@@ -115,6 +115,26 @@ inline hipError_t gdmk_set_lds_attr(const void *kernel, size_t lds, std::atomic<
   return e;
 }
 
+// Segments per line of one v3 line-solve pass (gdmk_launch_mass3: the grid's
+// second dimension; 1 = whole lines) and, in *seg_chunks, the chunks per
+// segment (0 = whole lines).  chunk = gdmk_mass3_chunk(p), seg_waves =
+// gdmk_mass3_seg_waves().  The one formula of the launcher and of what
+// gdm_op_mass_path reports.
+inline int gdmk_mass3_segments(int chunk, int len, int64_t n_lines, bool allow_segments, bool in_place,
+                               int seg_waves, int *seg_chunks) {
+  const int64_t grid = (n_lines + 63) / 64;
+  const int n_chunks = (len + chunk - 1) / chunk;
+  int sc = 0, n_segs = 1;
+  if (allow_segments && !in_place && grid < seg_waves && n_chunks >= 4) {
+    const int want = (int)(n_chunks < (1024 + grid - 1) / grid ? n_chunks : (1024 + grid - 1) / grid);
+    sc = (n_chunks + want - 1) / want;
+    n_segs = (n_chunks + sc - 1) / sc;
+    if (n_segs < 2) sc = 0, n_segs = 1;
+  }
+  if (seg_chunks) *seg_chunks = sc;
+  return n_segs;
+}
+
 }  // namespace gdmk
 
 extern "C" {

@@ -855,14 +855,9 @@ hipError_t launch_mass3_p(int dir_kind, const double *src, double *dst, int len,
   // (one wave per SIMD is the occupancy of these kernels, 1024 on the chip).
   // Segments read their neighbours' input chunks: only out of place (src != dst)
   constexpr int C = Geo3<P>::C;
-  const int n_chunks = (len + C - 1) / C;
-  int seg_chunks = 0, n_segs = 1;
-  if (allow_segments && src != dst && grid < GDM_MASS_SEG_WAVES && n_chunks >= 4) {
-    const int want = (int)std::min<int64_t>(n_chunks, (1024 + grid - 1) / grid);
-    seg_chunks = (n_chunks + want - 1) / want;
-    n_segs = (n_chunks + seg_chunks - 1) / seg_chunks;
-    if (n_segs < 2) seg_chunks = 0, n_segs = 1;
-  }
+  int seg_chunks = 0;
+  const int n_segs =
+      gdmk_mass3_segments(C, len, n_lines, allow_segments != 0, src == dst, GDM_MASS_SEG_WAVES, &seg_chunks);
   if (dir_kind == 0) {
     // <= 59 KB (p = 7): within the 64 KB default, no attribute needed
     constexpr size_t lds = Geo3<P>::lds_bytes();

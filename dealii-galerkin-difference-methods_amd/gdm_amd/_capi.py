@@ -86,6 +86,15 @@ class FieldTerm(ctypes.Structure):
     ]
 
 
+class MassPathPass(ctypes.Structure):
+    _fields_ = [("axis", ctypes.c_int), ("v3", ctypes.c_int), ("segments", ctypes.c_int), ("in_place", ctypes.c_int)]
+
+
+class MassPath(ctypes.Structure):
+    """gdm_mass_path: what the last line passes of the mass inverse launched"""
+    _fields_ = [("n_passes", ctypes.c_int), ("rk_mode", ctypes.c_int), ("passes", MassPathPass * 3)]
+
+
 FIELD_MAX_TERMS = 8
 
 _lib = None
@@ -148,6 +157,8 @@ def load():
         "gdm_mass_apply": [P, P, P],
         "gdm_mass_solve": [P, P, P],
         "gdm_mass_solve_rk": [P, P, d, P, P, d, P, P],
+        "gdm_op_set_mass_seg_waves": [P, i32],
+        "gdm_op_mass_path": [P, ctypes.POINTER(MassPath)],
         "gdm_mass_solve_periodic": [P, P, P],
         "gdm_mass_solve_periodic_rk": [P, P, d, P, P, d, P, P],
         "gdm_mass_periodic_tables": [ctypes.POINTER(MeshDesc), i32, P, P, ctypes.POINTER(ctypes.c_int),
@@ -201,6 +212,8 @@ def load():
         "gdm_csr_destroy": [P],
         "gdm_csr_info": [P, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)],
         "gdm_csr_set_stream": [P, P],
+        "gdm_csr_set_lanes": [P, i32],
+        "gdm_csr_kernel": [P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
         "gdm_csr_download": [P, P, P, P],
         "gdm_csr_vmult": [P, P, P],
         "gdm_csr_cg": [P, P, P, i32, i32, d, d, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],

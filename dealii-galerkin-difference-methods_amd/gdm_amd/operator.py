@@ -215,6 +215,22 @@ class GdmOperator:
               "gdm_mass_solve_rk")
         return acc_out
 
+    # -- dispatch control for tests and A/B runs -------------------------------
+    def set_mass_seg_waves(self, waves):
+        """passes of the mass inverse with fewer than `waves` waves of 64 lines
+        run segmented (gdm_op_set_mass_seg_waves): 0 = never, -1 = the default"""
+        check(self.lib.gdm_op_set_mass_seg_waves(self.h, int(waves)), "gdm_op_set_mass_seg_waves")
+
+    def mass_path(self):
+        """what the last mass inverse launched (gdm_op_mass_path): {"rk_mode":
+        0 or the fused kernel's variant 1 / 2 / 3, "passes": [{"axis", "v3",
+        "segments", "in_place"}, ...] in launch order}"""
+        mp = _capi.MassPath()
+        check(self.lib.gdm_op_mass_path(self.h, ctypes.byref(mp)), "gdm_op_mass_path")
+        return {"rk_mode": mp.rk_mode,
+                "passes": [{"axis": q.axis, "v3": bool(q.v3), "segments": q.segments, "in_place": bool(q.in_place)}
+                           for q in mp.passes[:mp.n_passes]]}
+
     def mass_solve(self, rhs_owned, x_owned):
         self._check_sizes(None, rhs_owned)
         self._check_sizes(None, x_owned)

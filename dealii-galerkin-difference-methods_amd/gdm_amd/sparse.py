@@ -126,6 +126,18 @@ class SparseMatrix:
         check(self._lib.gdm_csr_set_stream(self._h, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
               "gdm_csr_set_stream")
 
+    def set_lanes(self, K):
+        """SpMV kernel of vmult / solve_cg (gdm_csr_set_lanes): K in {2, 4, 8,
+        16, 32, 64} lanes per row, or 0 = the row-block kernel (the default)"""
+        check(self._lib.gdm_csr_set_lanes(self._h, int(K)), "gdm_csr_set_lanes")
+
+    def kernel(self):
+        """(mode, lanes) of the SpMV kernel in use (gdm_csr_kernel): (1, 0) =
+        row-block kernel, (0, K) = K lanes per row"""
+        mode, lanes = ctypes.c_int(-1), ctypes.c_int(-1)
+        check(self._lib.gdm_csr_kernel(self._h, ctypes.byref(mode), ctypes.byref(lanes)), "gdm_csr_kernel")
+        return mode.value, lanes.value
+
     def vmult(self, dst, src):
         """dst = A src (device fp64 tensors; deal.II argument order)."""
         m, n, _ = self._info()

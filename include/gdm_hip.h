@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GDM_HIP_ABI_VERSION 18
+#define GDM_HIP_ABI_VERSION 19
 
 enum gdm_status {
   GDM_OK = 0,
@@ -279,6 +279,45 @@ int gdm_mass_solve(gdm_op *op, const double *rhs_owned, double *x_owned);
  * Single rank, non-periodic (periodic: gdm_mass_solve_periodic_rk). */
 int gdm_mass_solve_rk(gdm_op *op, double *rhs_owned, double beta, const double *acc_in, double *acc_out,
                       double alpha, const double *y, double *Y);
+
+/* Dispatch control for tests and A/B runs (ABI 19).  Which kernels a mass
+ * inverse or an SpMV launches depends on sizes that small tests do not reach;
+ * these entry points steer that choice and report it.  None of them changes a
+ * result's bits beyond what the steered kernels are specified to give, and
+ * none changes the default dispatch.
+ *   gdm_op_set_mass_seg_waves   the line passes of the mass inverse (gdm_mass_solve,
+ *                        _rk, _periodic*, _slab) split the lines of a pass with
+ *                        fewer than `waves` waves of 64 lines into segments;
+ *                        waves in [0, default] (0: never segment; the default
+ *                        is one wave per SIMD of the chip, 1024), -1 restores
+ *                        the default; GDM_ERR_ARG otherwise.
+ *   gdm_op_mass_path     what the last line passes of this operator launched:
+ *                        per pass the kernel axis (0 = x, contiguous lines; 1,
+ *                        2 = y, z, strided lines; the one direction of a 1D
+ *                        mesh is kernel axis 2), v3 (single sweep) or v2 (two
+ *                        sweeps), the segments per line (1 = whole lines) and
+ *                        whether it ran in place;
+ *                        rk_mode = 0 when no RK update was fused into the last
+ *                        pass, else the fused kernel's variant: 1 = acc only,
+ *                        2 = acc and Y, 3 = acc and Y with acc_in == y.  A fused
+ *                        pass reports in_place = 0 (its result is not stored).
+ *                        n_passes = 0 before the first solve.
+ *   gdm_csr_set_lanes    K in {2, 4, 8, 16, 32, 64}: gdm_csr_vmult / gdm_csr_cg
+ *                        run the K-lanes-per-row kernel; K = 0: the row-block
+ *                        kernel (the default).  GDM_ERR_ARG otherwise.
+ *   gdm_csr_kernel       mode 1 / lanes 0: row-block kernel; mode 0 / lanes K. */
+typedef struct {
+  int n_passes; /* 0..3, in launch order */
+  int rk_mode;
+  struct {
+    int axis;     /* kernel axis of the pass: 0 = x, 1 = y, 2 = z */
+    int v3;       /* 1: single-sweep kernel, 0: two-sweep kernel */
+    int segments; /* segments per line; 1 = whole lines */
+    int in_place; /* the pass read and wrote the same buffer */
+  } pass[3];
+} gdm_mass_path;
+int gdm_op_set_mass_seg_waves(gdm_op *op, int waves);
+int gdm_op_mass_path(const gdm_op *op, gdm_mass_path *out);
 
 /* Exact mass inverse with periodicity constraints (ABI 17; replaces the
  * SolverCG + PreconditionJacobi of prototypes/advection_01_gdm.cc:208-217 by a
@@ -751,6 +790,9 @@ int gdm_csr_create(int device, int64_t n_rows, int64_t n_cols, int64_t nnz, cons
 int gdm_csr_destroy(gdm_csr *A);
 int gdm_csr_info(const gdm_csr *A, int64_t *n_rows, int64_t *n_cols, int64_t *nnz);
 int gdm_csr_set_stream(gdm_csr *A, void *hip_stream);
+/* kernel choice of gdm_csr_vmult / gdm_csr_cg (ABI 19; "dispatch control" above) */
+int gdm_csr_set_lanes(gdm_csr *A, int K);
+int gdm_csr_kernel(const gdm_csr *A, int *mode, int *lanes);
 /* host copies of the three arrays (caller-allocated, sizes from gdm_csr_info) */
 int gdm_csr_download(const gdm_csr *A, int64_t *row_ptr_host, uint32_t *cols_host, double *vals_host);
 /* dst = A src (device pointers, dst of n_rows, src of n_cols entries) */

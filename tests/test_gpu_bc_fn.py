@@ -81,12 +81,28 @@ def test_apply_bc_fn_argument_errors():
         wave.apply_bc_fn(wave.new_vector(local=True), wave.new_vector(local=False), 0, [1.0], 0.0)
 
 
-@pytest.mark.parametrize("dim,p,n", [(3, 5, 181), (3, 7, 183), (3, 3, 200), (2, 5, (300, 200)), (3, 5, 9)])
+# (axis, v3, segments per line) of every pass at the default segment threshold (1024 waves of 64 lines): 182^3 and
+# 184^3 vertices are 518 / 529 waves of 4-chunk lines, two segments each; 201 and 301 x vertices are odd, so the x
+# pass runs the two-sweep kernel; 10-vertex strided lines (no longer than a chunk) run it too
+RK_PATHS = {
+    (3, 5, 181): [(2, True, 2), (1, True, 2), (0, True, 2)],
+    (3, 7, 183): [(2, True, 2), (1, True, 2), (0, True, 2)],
+    (3, 3, 200): [(2, True, 2), (1, True, 2), (0, False, 1)],
+    (2, 5, (300, 200)): [(1, True, 5), (0, False, 1)],
+    (3, 5, 9): [(2, False, 1), (1, False, 1), (0, True, 1)],
+}
+
+
+@pytest.mark.parametrize("dim,p,n", list(RK_PATHS))
 @pytest.mark.parametrize("mode", ["Y", "noY", "alias"])
 def test_mass_solve_rk_bitwise_equals_separate(dim, p, n, mode):
-    """gdm_mass_solve_rk (the RK update fused into the x line-solve pass when
-    that pass runs unsegmented, 3D meshes with >= 32768 lines per pass; the
-    separate kernels otherwise) == gdm_mass_solve + gdm_vec_rk_update, bitwise"""
+    """gdm_mass_solve_rk == gdm_mass_solve + gdm_vec_rk_update, bitwise, where
+    the update is NOT fused: the fused x pass needs every pass unsegmented, at
+    the default threshold more than 65472 lines in every pass (256^3 vertices
+    and up; no 2D mesh of practical size), so at these sizes gdm_mass_solve_rk
+    runs the separate kernels behind segmented (or two-sweep) passes --
+    gdm_op_mass_path pins that.  The fused kernels:
+    tests/test_gpu_mass_dispatch.py."""
     import gdm_amd
 
     op = gdm_amd.GdmOperator(dim, p, n, 0.0, 1.0, "advection", params=(1.0, 0.15, -0.05)[:dim])
@@ -113,6 +129,9 @@ def test_mass_solve_rk_bitwise_equals_separate(dim, p, n, mode):
         op.mass_solve_rk(rhs2, beta, acc, acc_out)
     else:
         op.mass_solve_rk(rhs2, beta, acc_out, acc_out, alpha, y, Y)
+    path = op.mass_path()
+    assert path["rk_mode"] == 0, path
+    assert [(q["axis"], q["v3"], q["segments"]) for q in path["passes"]] == RK_PATHS[(dim, p, n)], path
     torch.cuda.synchronize()
     assert torch.equal(acc_out, acc_ref), float((acc_out - acc_ref).abs().max())
     if mode != "noY":

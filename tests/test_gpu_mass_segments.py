@@ -1,5 +1,5 @@
 """Segmented line solves of the exact mass inverse (gdm_mass.hip: a pass
-with fewer than 512 waves of lines splits every line into segments of >= 1
+with fewer than 1024 waves of lines splits every line into segments of >= 1
 chunk, each with a forward warm-up chunk before and a backward warm-up chunk
 after it, and the passes run out of place through a scratch vector).  The
 warm-ups start the recurrences from zero C = 48 / 48 / 56 positions (p = 3 /

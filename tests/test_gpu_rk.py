@@ -49,6 +49,26 @@ def test_rk_update():
     np.testing.assert_allclose(host(acc), a + 0.37 * k + 2.0 * k, rtol=1e-14, atol=1e-14)
 
 
+@pytest.mark.parametrize("n", [100003, 100004, 2, 1])
+@pytest.mark.parametrize("in_place", [False, True])
+def test_rk_update_y_is_acc_in(n, in_place):
+    """y is acc_in (the first RK stage): the host picks the kernel variant that
+    loads the shared vector once (gdmk_launch_rk_update).  Odd n ends in a
+    scalar tail element; in_place: acc_out is that shared vector too."""
+    import gdm_amd
+
+    op = gdm_amd.GdmOperator(1, 3, 40, 0.0, 1.0, "mass")
+    rng = np.random.default_rng(7)
+    k, a = (rng.uniform(-1, 1, n) for _ in range(2))
+    kd, ad = dev(k), dev(a)
+    acc = ad if in_place else torch.full_like(kd, float("nan"))
+    Y = torch.full_like(kd, float("nan"))
+    op.rk_update(0.37, kd, ad, acc, -1.25, ad, Y)
+    np.testing.assert_allclose(host(acc), a + 0.37 * k, rtol=1e-14, atol=1e-15)
+    np.testing.assert_allclose(host(Y), a - 1.25 * k, rtol=1e-14, atol=1e-15)
+    assert np.array_equal(host(kd), k)
+
+
 def _sine(pts, t, prm, dim, derivative):
     a, k, ph = prm[0:3], prm[3:6], prm[6:9]
     s = [np.sin(2 * np.pi * k[d] * (pts[:, d] - a[d] * t) + ph[d]) for d in range(dim)]

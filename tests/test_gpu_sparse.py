@@ -17,7 +17,7 @@
     device SpMV equals the same Kronecker operator applied as a 7x7 fp64
     stencil (49 shifted fp64 adds in torch) to <= 1e-13, and is linear.
 """
-import os
+import math
 
 import numpy as np
 import pytest
@@ -49,6 +49,16 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
+def _set_lanes(A, lanes):
+    """lanes "" = the default (row-block kernel), else K lanes per row
+    (gdm_csr_set_lanes); the matrix reports the kernel it will launch"""
+    if lanes:
+        A.set_lanes(int(lanes))
+        assert A.kernel() == (0, int(lanes))
+    else:
+        assert A.kernel() == (1, 0)
+
+
 def _vmult(A, x, m):
     y = torch.zeros(m, dtype=torch.float64, device="cuda")
     A.vmult(y, dev(x))
@@ -58,13 +68,12 @@ def _vmult(A, x, m):
 @pytest.mark.parametrize("dim,p,n", [(1, 3, 40), (2, 3, 12), (2, 5, 11), (3, 3, 6), (3, 5, 6)])
 @pytest.mark.parametrize("kind", [0, 1])
 @pytest.mark.parametrize("lanes", ["", "4", "16", "64"])
-def test_vmult_gdm_matrices_vs_oracle(dim, p, n, kind, lanes, monkeypatch):
-    if lanes:
-        monkeypatch.setenv("GDM_CSR_LANES", lanes)
+def test_vmult_gdm_matrices_vs_oracle(dim, p, n, kind, lanes):
     sp = _sp()
     m = O.Mesh(dim, p, n, 0.0, 1.0)
     rp, cols, vals = m.matrix_csr(kind=kind)
     A = sp.SparseMatrix(rp, cols.astype(np.uint32), vals)
+    _set_lanes(A, lanes)
     assert (A.m(), A.n(), A.n_nonzero_elements()) == (m.n_dofs, m.n_dofs, len(vals))
     x = np.random.default_rng(1).uniform(-1, 1, m.n_dofs)
     assert rel(_vmult(A, x, m.n_dofs), O.csr_vmult(rp, cols, vals, x)) < RTOL_SPMV
@@ -83,13 +92,12 @@ def _random_csr(rng, n_rows, n_cols, max_len, empty_frac=0.2):
 @pytest.mark.parametrize("n_rows,n_cols,max_len", [(1, 1, 1), (257, 257, 3), (1000, 700, 40), (300, 5000, 300),
                                                    (5000, 5000, 80), (64, 64, 0)])
 @pytest.mark.parametrize("lanes", ["", "2", "8", "32"])
-def test_vmult_ragged_vs_oracle(n_rows, n_cols, max_len, lanes, monkeypatch):
-    if lanes:
-        monkeypatch.setenv("GDM_CSR_LANES", lanes)
+def test_vmult_ragged_vs_oracle(n_rows, n_cols, max_len, lanes):
     sp = _sp()
     rng = np.random.default_rng(n_rows + max_len)
     rp, cols, vals = _random_csr(rng, n_rows, n_cols, max_len)
     A = sp.SparseMatrix(rp, cols, vals, n_cols=n_cols)
+    _set_lanes(A, lanes)
     x = rng.uniform(-1, 1, n_cols)
     y = _vmult(A, x, n_rows)
     ref = np.array([vals[rp[i]:rp[i + 1]] @ x[cols[rp[i]:rp[i + 1]]] for i in range(n_rows)])
@@ -97,6 +105,92 @@ def test_vmult_ragged_vs_oracle(n_rows, n_cols, max_len, lanes, monkeypatch):
         assert np.all(y == 0)
     else:
         assert rel(y, ref) < RTOL_SPMV
+
+
+def test_set_lanes_rejects_other_values_and_restores_the_default():
+    sp = _sp()
+    from gdm_amd import GdmError
+
+    A = sp.SparseMatrix(np.array([0, 1, 2], dtype=np.int64), np.array([0, 1], dtype=np.uint32), np.ones(2))
+    for K in (-1, 1, 3, 6, 48, 128):
+        with pytest.raises(GdmError):
+            A.set_lanes(K)
+        assert A.kernel() == (1, 0)
+    A.set_lanes(8)
+    assert A.kernel() == (0, 8)
+    A.set_lanes(0)
+    assert A.kernel() == (1, 0)
+
+
+# row lengths: a row of exactly CSR_NZB = 1024 entries fills a row block's LDS products, one of 1025 or 3000 is
+# reduced by the whole workgroup; each between short and empty rows, each once as the last row.  600 one-entry rows:
+# the 256-rows-per-block cap gives 3 blocks (the XCD block order's tail, n_blocks % 8 != 0)
+ROW_LENGTHS = {
+    "between": [5, 0, 1024, 3, 0, 1025, 7, 0, 3000, 2, 0],
+    "last-1024": [4, 0, 3000, 1, 0, 1025, 0, 6, 1024],
+    "last-1025": [0, 1024, 2, 0, 3000, 9, 0, 1025],
+    "last-3000": [1025, 0, 1, 1024, 0, 3, 3000],
+    "600x1": [1] * 600,
+}
+
+
+@pytest.mark.parametrize("case", list(ROW_LENGTHS))
+@pytest.mark.parametrize("lanes", ["", "4", "64"])
+def test_vmult_long_rows_vs_fsum(case, lanes):
+    """Per row against math.fsum of the products, within the standard bound of
+    recursive summation in any order: |y_i - ref_i| <= n_i 2^-52 sum_k |v_k
+    x_k| (n_i: the row's length; an empty row gives exactly 0)."""
+    sp = _sp()
+    lens = np.array(ROW_LENGTHS[case], dtype=np.int64)
+    n_rows, n_cols = len(lens), 4000
+    rng = np.random.default_rng(len(case) + n_rows)
+    rp = np.zeros(n_rows + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(lens)
+    cols = np.concatenate([np.sort(rng.choice(n_cols, l, replace=False)) for l in lens]).astype(np.int64)
+    vals = rng.uniform(-1, 1, int(rp[-1]))
+    A = sp.SparseMatrix(rp, cols, vals, n_cols=n_cols)
+    _set_lanes(A, lanes)
+    x = rng.uniform(-1, 1, n_cols)
+    y = _vmult(A, x, n_rows)
+    prod = vals * x[cols]
+    ref = np.array([math.fsum(prod[rp[i]:rp[i + 1]]) for i in range(n_rows)])
+    bound = lens * 2.0 ** -52 * np.array([math.fsum(np.abs(prod[rp[i]:rp[i + 1]])) for i in range(n_rows)])
+    excess = np.abs(y - ref) - bound
+    assert np.all(excess <= 0), (int(np.argmax(excess)), float(np.max(excess)))
+    assert rel(y, ref) < RTOL_SPMV
+
+
+@pytest.mark.parametrize("precond", ["identity", "jacobi"])
+@pytest.mark.parametrize("lanes", ["", "16"])
+def test_cg_arrowhead_long_row(precond, lanes):
+    """SPD arrowhead matrix, n = 1500: a dense first row and column (1500
+    entries: the row-block kernel's one-long-row branch, in CG's residual
+    launch b - A x0 with x0 != 0 and in every iteration's matvec) and the
+    diagonal 2 x (the row's absolute off-diagonal sum); against
+    numpy.linalg.solve at test_cg_vs_oracle's tolerance for rel_tol 1e-14."""
+    sp = _sp()
+    n = 1500
+    rng = np.random.default_rng(15)
+    a = rng.uniform(0.5, 1.0, n - 1) * rng.choice([-1.0, 1.0], n - 1)
+    D = np.zeros((n, n))
+    D[0, 1:] = a
+    D[1:, 0] = a
+    D[np.arange(n), np.arange(n)] = 2 * np.abs(D).sum(axis=1)
+    rows, cc = np.nonzero(D)
+    rp = np.zeros(n + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    assert rp[1] == n > 1024
+    vals = D[rows, cc]
+    b = rng.uniform(-1, 1, n)
+    x_ref = np.linalg.solve(D, b)
+    A = sp.SparseMatrix(rp, cc.astype(np.uint32), vals)
+    _set_lanes(A, lanes)
+    x0 = rng.uniform(-1, 1, n)
+    x = dev(x0)
+    its, res = sp.solve_cg(A, x, dev(b), preconditioner=precond, max_it=5000, abs_tol=1e-20, rel_tol=1e-14)
+    assert its > 0
+    assert res <= 1e-14 * np.linalg.norm(b - D @ x0) * (1 + 1e-6)
+    assert rel(host(x), x_ref) < 1e-10
 
 
 def test_device_arrays_equal_host_arrays():

@@ -96,7 +96,7 @@ def test_outer_product_of_1d_load_vectors_is_the_sine_load(dim, p, n_sub):
 
 def test_pure_host_entry_points_check_their_arguments():
     L = _capi.load()
-    assert L.gdm_abi_version() == 18
+    assert L.gdm_abi_version() == 19
     mesh = _capi.mesh_desc(2, 3, [5, 4])
     b = np.zeros(8)
     bp = b.ctypes.data_as(ctypes.c_void_p)

@@ -8,8 +8,10 @@ SpMV cost depends on the structure only.
 
 Algorithmic bytes per SpMV: 12 B per stored entry (u32 column + f64 value)
 + 24 B per row (int64 row pointer, x read once, y written once).
-One JSON line on stdout.
+--lanes K runs the K-lanes-per-row kernel (2, 4, 8, 16, 32, 64) in place of
+the row-block default (0).  One JSON line on stdout.
 """
+import argparse
 import json
 import os
 import sys
@@ -23,6 +25,9 @@ def main():
     import torch
     from gdm_amd import sparse as sp
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lanes", type=int, default=0, choices=[0, 2, 4, 8, 16, 32, 64])
+    args = ap.parse_args()
     n = int(os.environ.get("GDM_CSR_N", "4096"))
     p = 3
     m = np.array([1.0, 4.0, 9.0, 16.0, 9.0, 4.0, 1.0])
@@ -31,6 +36,8 @@ def main():
     rp, ci, v = sp.stencil_csr_2d(n, p, [(lap, m), (m, lap)])
     A = sp.SparseMatrix(rp, ci, v)
     del rp, ci, v
+    A.set_lanes(args.lanes)
+    mode, lanes = A.kernel()
     torch.cuda.empty_cache()
     rows, nnz = A.m(), A.n_nonzero_elements()
     gen = torch.Generator(device="cuda").manual_seed(20251010)
@@ -56,7 +63,7 @@ def main():
     b_norm = float(torch.linalg.norm(b))
     out = {
         "metric": "CSR vmult (cut-Poisson CG matvec, config 5)",
-        "n_rows": rows, "nnz": nnz, "lanes": os.environ.get("GDM_CSR_LANES", "auto"),
+        "n_rows": rows, "nnz": nnz, "kernel": "row-block" if mode == 1 else "lanes", "lanes": lanes,
         "spmv_ms": ms, "rows_per_s": rows / (ms * 1e-3),
         "roofline": {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
                      "frac": alg / (ms * 1e-3) / 1e9 / 8000.0, "algorithmic_bytes_per_launch": alg},
