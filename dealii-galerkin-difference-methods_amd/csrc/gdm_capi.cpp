@@ -25,6 +25,7 @@
 #include "gdm_post.h"
 #include "gdm_rk.h"
 #include "gdm_setup.h"
+#include "gdm_vardiff.h"
 #include "gdm_varstencil.h"
 
 namespace {
@@ -207,6 +208,20 @@ struct gdm_op {
     std::vector<std::vector<double>> face_end;
     std::vector<void *> allocations;
   } field;
+  // separable coefficient of the wave operator (gdm_op_set_coefficient): the
+  // launch plan of gdm_vardiff.hip, kappa at the boundary points with the
+  // scratch of kappa g, the domain mean of kappa and the CG vectors of
+  // gdm_coef_solve, all device memory allocated when the coefficient is set
+  struct Coef {
+    bool active = false;
+    int n_terms = 0;
+    gdmk::DiffArgs args{};  // src / dst filled per apply
+    size_t lds = 0;
+    double *kappa_bc = nullptr, *g_scaled = nullptr;  // [n_bc_points]
+    double mean = 1.0;
+    double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, M p
+    std::vector<void *> allocations;
+  } coef;
   bool cut_inner = false;  // the inner operator of a cut handle
   // load vector / Dirichlet data (gdm_add_load*, gdm_add_dirichlet_data; single
   // rank, non-periodic): shape values times quadrature weights per category,
@@ -246,6 +261,7 @@ void free_op(gdm_op *op) {
   if (!op) return;
   for (void *ptr : op->allocations) (void)hipFree(ptr);
   for (void *ptr : op->field.allocations) (void)hipFree(ptr);
+  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
   if (op->own_stream) (void)hipStreamDestroy(op->own_stream);
   delete op;
 }
@@ -2019,6 +2035,121 @@ void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::F
 }
 
 const char *kFieldPlanes = "gdm_apply_planes: not with a separable advection field (gdm_op_set_advection_field)";
+const char *kCoefPlanes = "gdm_apply_planes: not with a separable coefficient (gdm_op_set_coefficient)";
+
+// ---- separable coefficient of the wave operator (gdm_vardiff.hip) -----------
+
+void coef_apply(gdm_op *op, const double *src, double *dst) {
+  gdmk::DiffArgs a = op->coef.args;
+  a.src = src;
+  a.dst = dst;
+  hip_check(gdmk::launch_diff(op->p, a, op->coef.lds, op->stream), "coefficient apply launch");
+}
+
+// samples of a factor along direction d
+size_t coef_samples(const gdm_mesh_desc *mesh, int d) {
+  return (size_t)mesh->n_subdivisions[d] * (mesh->fe_degree + 1) + 2;
+}
+
+// Build the launch plan, tables and scratch of a coefficient into `nc` (every
+// device allocation is recorded in nc.allocations as it is made).
+void build_coef(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::Coef &nc) {
+  const int p = op->p, W = 2 * p + 1, n1 = p + 1;
+  auto up = [&](const std::vector<double> &h) {
+    double *d = dev_upload(h);
+    nc.allocations.push_back(d);
+    return d;
+  };
+  nc.n_terms = n_terms;
+  const double noh = nitsche_over_hmin(&op->mesh, op->nitsche);
+  // distinct device tables: (kernel axis, M or B, factor array); terms that
+  // pass the same array share them
+  struct Table {
+    int ax, which;
+    const double *f;
+    double *dev;
+  };
+  std::vector<Table> tabs;
+  auto table = [&](int ax, int which, const double *f) -> const double * {
+    const int d = op->kdir[ax];
+    if (d < 0) f = nullptr;
+    for (const Table &T : tabs)
+      if (T.ax == ax && T.which == which && T.f == f) return T.dev;
+    gdm::Band B(1, p);
+    if (d < 0) {
+      if (which == 0) B(0, 0) = 1.0;  // a trivial axis: M = (1), B = (0)
+    } else {
+      const unsigned ncell = (unsigned)op->mesh.n_subdivisions[d];
+      const double h = (op->mesh.hi[d] - op->mesh.lo[d]) / ncell;
+      B = which ? gdm::wave_band_1d_weighted(p, ncell, h, noh, f)
+                : gdm::assemble_1d_weighted(p, ncell, h, f ? f + 1 : nullptr).M;
+    }
+    // x: the plain rows; y: zero rows up to a whole tile; z: p zero rows in front and behind
+    const size_t rows = ax == 0 ? B.n : (ax == 1 ? gdmk::diff_y_rows(B.n) : B.n + 2 * p);
+    std::vector<double> t(rows * W, 0.0);
+    std::copy(B.a.begin(), B.a.end(), t.begin() + (ax == 2 ? (size_t)p * W : 0));
+    tabs.push_back(Table{ax, which, f, up(t)});
+    return tabs.back().dev;
+  };
+  gdmk::DiffArgs &a = nc.args;
+  a = gdmk::DiffArgs{};
+  a.Nx = op->K[0];
+  a.Ny = op->K[1];
+  a.Nz = op->K[2];
+  a.n_terms = n_terms;
+  for (int t = 0; t < n_terms; ++t) {
+    const double *f[3];
+    for (int ax = 0; ax < 3; ++ax) f[ax] = op->kdir[ax] < 0 ? nullptr : terms[t].factor[op->kdir[ax]];
+    a.xm[t] = table(0, 0, f[0]);
+    a.xb[t] = table(0, 1, f[0]);
+    a.ym[t] = table(1, 0, f[1]);
+    a.yb[t] = table(1, 1, f[1]);
+    a.zm[t] = table(2, 0, f[2]);
+    a.zb[t] = table(2, 1, f[2]);
+  }
+  nc.lds = gdmk::diff_lds(p, n_terms);
+  if (nc.lds > 160 * 1024) throw std::runtime_error("coefficient: the launch plan exceeds the LDS of a CU");
+  hip_check(gdmk::diff_prepare(p, nc.lds), "coefficient: LDS limit");
+
+  // the domain mean: sum_t prod_d mean(k_td), the Gauss weights sum to 1 per cell
+  std::vector<double> xq, wq;
+  gdm::gauss_unit(n1, xq, wq);
+  nc.mean = 0.0;
+  for (int t = 0; t < n_terms; ++t) {
+    double prod = 1.0;
+    for (int d = 0; d < op->dim; ++d) {
+      const double *f = terms[t].factor[d];
+      if (!f) continue;
+      const int ncell = op->mesh.n_subdivisions[d];
+      double s = 0.0;
+      for (int c = 0; c < ncell; ++c)
+        for (int q = 0; q < n1; ++q) s += wq[q] * f[1 + (size_t)c * n1 + q];
+      prod *= s / ncell;
+    }
+    nc.mean += prod;
+  }
+
+  // kappa at the boundary points: Gauss entries in the tangential directions,
+  // the lo / hi entry in the normal one
+  const int64_t nbc = op->layout.n_bc_points;
+  std::vector<double> kbc((size_t)std::max<int64_t>(nbc, 1), 0.0);
+  for (const Face &F : op->faces) {
+    const int e0 = F.t0.dim_index, e1 = F.t1.dim_index;
+    for (int t = 0; t < n_terms; ++t) {
+      const double *fn = terms[t].factor[F.d];
+      const double end = fn ? fn[F.side ? coef_samples(&op->mesh, F.d) - 1 : 0] : 1.0;
+      const double *f0 = e0 < 0 ? nullptr : terms[t].factor[e0], *f1 = e1 < 0 ? nullptr : terms[t].factor[e1];
+      for (int64_t i1 = 0; i1 < F.t1.Q; ++i1)
+        for (int64_t i0 = 0; i0 < F.t0.Q; ++i0)
+          kbc[(size_t)(F.offset + i1 * F.t0.Q + i0)] += end * (f0 ? f0[1 + i0] : 1.0) * (f1 ? f1[1 + i1] : 1.0);
+    }
+  }
+  nc.kappa_bc = up(kbc);
+  nc.g_scaled = up(std::vector<double>(kbc.size(), 0.0));
+  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
+  for (double *&v : nc.cg) v = up(std::vector<double>(n, 0.0));
+  nc.active = true;
+}
 }  // namespace
 
 int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const double *bc_values) {
@@ -2028,10 +2159,15 @@ int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const doub
     if (bc_values) return fail(GDM_ERR_ARG, "gdm_apply: an elasticity operator takes no boundary values");
     if (src_local == dst_owned) return fail(GDM_ERR_ARG, "gdm_apply: src and dst must be distinct vectors");
   }
+  if (op->coef.active && bc_values)
+    return fail(GDM_ERR_ARG, "gdm_apply: a wave operator with a coefficient takes no boundary values "
+                             "(gdm_add_dirichlet_data adds the data term)");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
   if (op->kind == GDM_OP_ELASTICITY) {
     elasticity_apply(op, src_local, dst_owned);
+  } else if (op->coef.active) {
+    coef_apply(op, src_local, dst_owned);
   } else if (op->field.active) {
     field_apply(op, src_local, dst_owned, bc_values);
   } else if (op->concurrent && !op->mesh.periodic) {
@@ -2052,6 +2188,7 @@ int gdm_apply_planes(gdm_op *op, const double *src_local, double *dst_owned, int
   if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: periodic constraints");
   if (op->kind == GDM_OP_ELASTICITY) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes: not for elasticity operators");
   if (op->field.active) return fail(GDM_ERR_UNSUPPORTED, kFieldPlanes);
+  if (op->coef.active) return fail(GDM_ERR_UNSUPPORTED, kCoefPlanes);
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
   hip_check(launch_stencil(op, op->kind == GDM_OP_MASS, src_local, dst_owned, plane_begin, plane_end),
@@ -2067,6 +2204,7 @@ int gdm_apply_planes2(gdm_op *op, const double *src_local, double *dst_owned, in
   if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: periodic constraints");
   if (op->kind == GDM_OP_ELASTICITY) return fail(GDM_ERR_UNSUPPORTED, "gdm_apply_planes2: not for elasticity operators");
   if (op->field.active) return fail(GDM_ERR_UNSUPPORTED, kFieldPlanes);
+  if (op->coef.active) return fail(GDM_ERR_UNSUPPORTED, kCoefPlanes);
   // clip both ranges to the owned planes first (a first range in
   // the ghost planes must not drop the second), then test overlap and emptiness
   {
@@ -2185,6 +2323,75 @@ int gdm_op_set_field_scale(gdm_op *op, const double *s) {
   if (!op->field.active) return fail(GDM_ERR_STATE, "gdm_op_set_field_scale: no advection field is set");
   for (int t = 0; t < op->field.n_terms; ++t) op->field.scale[t] = s[t];
   return GDM_OK;
+}
+
+int gdm_coef_matrix_1d(const gdm_mesh_desc *mesh, double nitsche, int axis, int which, const double *f,
+                       double *band_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  if (!band_host) return fail(GDM_ERR_ARG, "band_host is NULL");
+  if (which != 0 && which != 1) return fail(GDM_ERR_ARG, "which: 0 = M[f], 1 = B[f]");
+  if (!std::isfinite(nitsche)) return fail(GDM_ERR_ARG, "nitsche is not finite");
+  for (int d = 0; d < mesh->dim; ++d)
+    if (mesh->n_subdivisions[d] < 1 || !(mesh->hi[d] > mesh->lo[d])) return fail(GDM_ERR_ARG, "empty box");
+  GDM_GUARD_BEGIN
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  const double h = (mesh->hi[axis] - mesh->lo[axis]) / nc;
+  const gdm::Band B = which ? gdm::wave_band_1d_weighted(mesh->fe_degree, nc, h, nitsche_over_hmin(mesh, nitsche), f)
+                            : gdm::assemble_1d_weighted(mesh->fe_degree, nc, h, f ? f + 1 : nullptr).M;
+  std::copy(B.a.begin(), B.a.end(), band_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_coef_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (tile_x) *tile_x = gdmk::DIFF_TX;
+  if (tile_y) *tile_y = gdmk::DIFF_TY;
+  if (z_chunk) *z_chunk = gdmk::DIFF_ZC;
+  return GDM_OK;
+}
+
+int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: wave operators only");
+  if (op->cut_inner)
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: the cut-cell rows of a cut handle are assembled for "
+                                     "the constant coefficient");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: single rank only");
+  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: not with periodic constraints");
+  if (n_terms < 0 || n_terms > GDM_COEF_MAX_TERMS)
+    return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: n_terms must be in [0, GDM_COEF_MAX_TERMS]");
+  if (n_terms > 0 && !terms) return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: terms is NULL");
+  for (int t = 0; t < n_terms; ++t)
+    for (int d = 0; d < op->dim; ++d) {
+      const double *f = terms[t].factor[d];
+      if (!f) continue;
+      const size_t n = coef_samples(&op->mesh, d);
+      for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(f[i])) return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: a factor sample is not finite");
+        // one term: kappa > 0 needs factors that keep their sign and never vanish
+        if (n_terms == 1 && !(f[i] * f[0] > 0.0))
+          return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: a factor of a one-term coefficient vanishes or changes sign");
+      }
+    }
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  gdm_op::Coef nc;
+  if (n_terms > 0) {
+    try {
+      build_coef(op, n_terms, terms, nc);
+    } catch (...) {
+      for (void *ptr : nc.allocations) (void)hipFree(ptr);
+      throw;
+    }
+  }
+  // applies in flight read the old tables
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
+  op->coef = std::move(nc);
+  return GDM_OK;
+  GDM_GUARD_END
 }
 
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned) {
@@ -2920,6 +3127,12 @@ int gdm_add_dirichlet_data(gdm_op *op, const double *g_bc, double *dst_owned) {
     hmin = std::min(hmin, h[d]);
   }
   const int64_t stride[3] = {1, op->N[0], (int64_t)op->N[0] * op->N[1]};
+  if (op->coef.active) {
+    // the data term is linear in kappa g (wave/stiffness.h:312-327 with JxW multiplied by kappa)
+    hip_check(gdmk_launch_vmul(op->layout.n_bc_points, op->coef.kappa_bc, g_bc, op->coef.g_scaled, op->stream),
+              "kappa g");
+    g_bc = op->coef.g_scaled;
+  }
   // one launch per face, stream-ordered: the faces share the (p+1)-deep edge and corner columns
   for (const Face &F : op->faces) {
     gdmk::DirFace A{};
@@ -3098,10 +3311,13 @@ int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *sr
   GDM_GUARD_END
 }
 
-int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned) {
-  if (int rc = check_fastdiag_op(op, "gdm_system_solve", true)) return rc;
-  if (!rhs_owned || !x_owned) return fail(GDM_ERR_ARG, "NULL vector");
-  if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_system_solve: alpha / tau is not finite");
+}  // extern "C"
+
+namespace {
+
+// x = (alpha M + tau S)^-1 rhs of the constant-coefficient operator by fast
+// diagonalisation: gdm_system_solve, and the preconditioner of gdm_coef_solve
+int fastdiag_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned) {
   // the spectrum of alpha M + tau S in the M-orthonormal eigenbasis is alpha + tau sum_d lambda_d
   double smin = 0.0, smax = 0.0;
   int axes[3], n_axes = 0;
@@ -3153,6 +3369,89 @@ int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_own
     src = dst;
   }
   return GDM_OK;
+  GDM_GUARD_END
+}
+
+}  // namespace
+
+extern "C" {
+
+int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned) {
+  if (int rc = check_fastdiag_op(op, "gdm_system_solve", true)) return rc;
+  if (!rhs_owned || !x_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_system_solve: alpha / tau is not finite");
+  if (op->coef.active)
+    return fail(GDM_ERR_STATE, "gdm_system_solve: the direct solve is the constant-coefficient one; with a "
+                               "coefficient set use gdm_coef_solve");
+  return fastdiag_solve(op, alpha, tau, rhs_owned, x_owned);
+}
+
+int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, double *x, double rel_tol, double abs_tol,
+                   int max_it, int *its_host, double *res_host) {
+  if (int rc = check_fastdiag_op(op, "gdm_coef_solve", false)) return rc;
+  if (!op->coef.active) return fail(GDM_ERR_STATE, "gdm_coef_solve: no coefficient is set (gdm_op_set_coefficient)");
+  if (!op->fd.built) return fail(GDM_ERR_STATE, "gdm_coef_solve: call gdm_system_solve_setup first (the preconditioner)");
+  if (!rhs || !x || rhs == x) return fail(GDM_ERR_ARG, "rhs and x: distinct device vectors");
+  if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_coef_solve: alpha / tau is not finite");
+  if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const int64_t n = op->layout.n_owned;
+  double *r = op->coef.cg[0], *p = op->coef.cg[1], *Ap = op->coef.cg[2], *z = op->coef.cg[3], *Mp = op->coef.cg[4];
+  const double ptau = tau * op->coef.mean;
+  auto dot = [&](const double *u, const double *v) {
+    double s = 0.0;
+    if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
+    return s;
+  };
+  // dst = (alpha M - tau K[kappa]) src
+  auto apply = [&](const double *src, double *dst) {
+    coef_apply(op, src, dst);
+    if (alpha != 0.0) {
+      any_stencil(op, true, src, Mp);
+      hip_check(gdmk_launch_axpby(n, alpha, Mp, -tau, dst, op->stream), "axpby");
+    } else {
+      hip_check(gdmk_launch_axpby(n, 0.0, src, -tau, dst, op->stream), "axpby");
+    }
+  };
+  // SolverCG with ReductionControl(max_it, abs_tol, rel_tol), x the initial
+  // guess, preconditioned by (alpha M - tau mean(kappa) K_0)^-1
+  apply(x, r);
+  hip_check(gdmk_launch_axpby(n, 1.0, rhs, -1.0, r, op->stream), "axpby");
+  double res = std::sqrt(dot(r, r));
+  const double tol = std::max(abs_tol, rel_tol * res);
+  int it = 0;
+  auto done = [&](int code, const char *msg) {
+    if (its_host) *its_host = it;
+    if (res_host) *res_host = res;
+    return code == GDM_OK ? GDM_OK : fail(code, msg);
+  };
+  if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_coef_solve: the residual is not finite");
+  if (res > tol) {
+    if (int rc = fastdiag_solve(op, alpha, ptau, r, z)) return rc;
+    hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
+    double rz = dot(r, z);
+    while (true) {
+      if (it >= max_it) return done(GDM_ERR_STATE, "gdm_coef_solve: max_it reached (SolverControl::NoConvergence)");
+      ++it;
+      apply(p, Ap);
+      const double pAp = dot(p, Ap);
+      if (!(pAp > 0.0))
+        return done(GDM_ERR_STATE, "gdm_coef_solve: breakdown (p^T A p <= 0): alpha M - tau K[kappa] is not positive "
+                                   "definite; kappa must be positive on the box");
+      const double step = rz / pAp;
+      hip_check(gdmk_launch_axpby(n, step, p, 1.0, x, op->stream), "axpby");
+      hip_check(gdmk_launch_axpby(n, -step, Ap, 1.0, r, op->stream), "axpby");
+      res = std::sqrt(dot(r, r));
+      if (res <= tol) break;
+      if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_coef_solve: the residual is not finite");
+      if (int rc = fastdiag_solve(op, alpha, ptau, r, z)) return rc;
+      const double rz_new = dot(r, z);
+      hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
+      rz = rz_new;
+    }
+  }
+  return done(GDM_OK, "");
   GDM_GUARD_END
 }
 

@@ -123,7 +123,7 @@ Matrices1D assemble_1d(int p, unsigned n_cells, double h) {
 WeightedMatrices1D assemble_1d_weighted(int p, unsigned n_cells, double h, const double *f) {
   if (n_cells < (unsigned)p) throw std::invalid_argument("n_subdivisions must be >= fe_degree");
   const int n1 = p + 1, N = int(n_cells) + 1;
-  WeightedMatrices1D m{Band(N, p), Band(N, p)};
+  WeightedMatrices1D m{Band(N, p), Band(N, p), Band(N, p)};
   std::vector<double> xq, wq;
   gauss_unit(n1, xq, wq);
   const int ncat = std::max(1, p);
@@ -142,20 +142,23 @@ WeightedMatrices1D assemble_1d_weighted(int p, unsigned n_cells, double h, const
     const double *fc = f ? f + (size_t)c * n1 : nullptr;
     for (int i = 0; i < n1; ++i)
       for (int j = 0; j < n1; ++j) {
-        double mm = 0, cc = 0;
+        double mm = 0, cc = 0, ll = 0;
         for (int q = 0; q < n1; ++q) {
           // f == 1 takes assemble_1d's arithmetic, so its bits
           const double jxw = wq[q] * h;
           if (fc) {
             mm += v[i * n1 + q] * v[j * n1 + q] * (jxw * fc[q]);
             cc += g[i * n1 + q] * v[j * n1 + q] * (jxw * fc[q]);
+            ll += g[i * n1 + q] * g[j * n1 + q] * (jxw * fc[q]);
           } else {
             mm += v[i * n1 + q] * v[j * n1 + q] * jxw;
             cc += g[i * n1 + q] * v[j * n1 + q] * jxw;
+            ll += g[i * n1 + q] * g[j * n1 + q] * jxw;
           }
         }
         m.M(off + i, off + j) += mm;
         m.C(off + i, off + j) += cc;
+        m.L(off + i, off + j) += ll;
       }
   }
   return m;
@@ -235,6 +238,34 @@ Band wave_band_1d(int p, unsigned n_cells, double h, double nitsche_over_hmin, c
           const double di = shape_1d(p, cat, ii, x, 1) / h * nrm;
           const double dj = shape_1d(p, cat, jj, x, 1) / h * nrm;
           b(off + ii, off + jj) -= (-di * vj - vi * dj + nitsche_over_hmin * vi * vj);
+        }
+    }
+  }
+  return b;
+}
+
+Band wave_band_1d_weighted(int p, unsigned n_cells, double h, double nitsche_over_hmin, const double *f) {
+  const WeightedMatrices1D m = assemble_1d_weighted(p, n_cells, h, f ? f + 1 : nullptr);
+  const int n = m.M.n, last = n - 1;
+  Band b(n, p);
+  for (int i = 0; i < n; ++i)
+    for (int j = std::max(0, i - p); j <= std::min(last, i + p); ++j) b(i, j) = -m.L(i, j);
+  if (nitsche_over_hmin > 0.0) {
+    const unsigned cl = 0, cr = n_cells - 1;
+    const int catl = (int)category(cl, p, n_cells), catr = (int)category(cr, p, n_cells);
+    const int offl = (int)box_offset(cl, p, n_cells), offr = (int)box_offset(cr, p, n_cells);
+    const size_t n_samples = (size_t)n_cells * (p + 1) + 2;
+    for (int side = 0; side < 2; ++side) {
+      const int cat = side ? catr : catl, off = side ? offr : offl;
+      const double x = side ? 1.0 : 0.0, nrm = side ? 1.0 : -1.0;
+      for (int ii = 0; ii <= p; ++ii)
+        for (int jj = 0; jj <= p; ++jj) {
+          const double vi = shape_1d(p, cat, ii, x, 0), vj = shape_1d(p, cat, jj, x, 0);
+          const double di = shape_1d(p, cat, ii, x, 1) / h * nrm;
+          const double dj = shape_1d(p, cat, jj, x, 1) / h * nrm;
+          // f == 1 takes wave_band_1d's arithmetic, so its bits
+          const double blk = -di * vj - vi * dj + nitsche_over_hmin * vi * vj;
+          b(off + ii, off + jj) -= f ? f[side ? n_samples - 1 : 0] * blk : blk;
         }
     }
   }

@@ -86,6 +86,11 @@ class FieldTerm(ctypes.Structure):
     ]
 
 
+class CoefTerm(ctypes.Structure):
+    """gdm_coef_term: one term k_0(x_0) k_1(x_1) k_2(x_2) of a coefficient"""
+    _fields_ = [("factor", ctypes.c_void_p * 3)]
+
+
 class MassPathPass(ctypes.Structure):
     _fields_ = [("axis", ctypes.c_int), ("v3", ctypes.c_int), ("segments", ctypes.c_int), ("in_place", ctypes.c_int)]
 
@@ -96,6 +101,7 @@ class MassPath(ctypes.Structure):
 
 
 FIELD_MAX_TERMS = 8
+COEF_MAX_TERMS = 4
 
 _lib = None
 
@@ -154,6 +160,11 @@ def load():
                            ctypes.POINTER(ctypes.c_int)],
         "gdm_op_set_advection_field": [P, i32, P],
         "gdm_op_set_field_scale": [P, P],
+        "gdm_coef_matrix_1d": [ctypes.POINTER(MeshDesc), d, i32, i32, P, P],
+        "gdm_coef_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                          ctypes.POINTER(ctypes.c_int)],
+        "gdm_op_set_coefficient": [P, i32, P],
+        "gdm_coef_solve": [P, d, d, P, P, d, d, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
         "gdm_mass_apply": [P, P, P],
         "gdm_mass_solve": [P, P, P],
         "gdm_mass_solve_rk": [P, P, d, P, P, d, P, P],
@@ -333,6 +344,35 @@ def field_tile(fe_degree):
     """(tile_x, tile_y, z_chunk) of the separable field's volume kernel, kernel axes"""
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_field_tile(int(fe_degree), *[ctypes.byref(v) for v in t]), "gdm_field_tile")
+    return tuple(v.value for v in t)
+
+
+def coef_matrix_1d(mesh, nitsche, axis, which, f=None):
+    """Band [n_sub + 1][2p+1] of M[f] (which = 0) or B[f] (which = 1) of the wave
+    operator with a coefficient factor f along `axis` (gdm_coef_matrix_1d); f
+    sampled at field_points (None: f = 1).  Pure host, no GPU."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("coef_matrix_1d: axis outside [0, dim)")
+    n = mesh.n_subdivisions[axis]
+    fp = None
+    if f is not None:
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.size != n * (mesh.fe_degree + 1) + 2:
+            raise GdmError("coef_matrix_1d: f has %d samples, field_points has %d"
+                           % (f.size, n * (mesh.fe_degree + 1) + 2))
+        fp = f.ctypes.data_as(ctypes.c_void_p)
+    band = np.zeros((n + 1, 2 * mesh.fe_degree + 1))
+    check(load().gdm_coef_matrix_1d(ctypes.byref(mesh), float(nitsche), int(axis), int(which), fp,
+                                    band.ctypes.data_as(ctypes.c_void_p)), "gdm_coef_matrix_1d")
+    return band
+
+
+def coef_tile(fe_degree, dim):
+    """(tile_x, tile_y, z_chunk) of the coefficient kernel, kernel axes"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_coef_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_coef_tile")
     return tuple(v.value for v in t)
 
 

@@ -400,6 +400,59 @@ class GdmOperator:
               "gdm_system_solve")
         return x_owned
 
+    # -- separable coefficient of the wave / heat / Poisson operator ---------------
+    def set_coefficient(self, terms):
+        """kappa(x) = sum of the terms [k0, k1, k2] of products k0(x_0) k1(x_1)
+        k2(x_2) (gdm_op_set_coefficient; wave operators).  A factor is an array
+        sampled at field_points(axis), a callable evaluated there, or None
+        (= 1).  Terms that pass the same array object share its tables.  An
+        empty list restores the constant operator."""
+        terms = [list(t) for t in terms]
+        if len(terms) > _capi.COEF_MAX_TERMS:
+            raise GdmError("set_coefficient: at most %d terms" % _capi.COEF_MAX_TERMS)
+        arr = (_capi.CoefTerm * max(len(terms), 1))()
+        keep = {}  # (id(factor object), axis) -> sampled array: object identity becomes pointer identity
+        for t, factors in enumerate(terms):
+            factors = factors + [None] * (3 - len(factors))
+            for d in range(3):
+                f = factors[d]
+                if f is None or d >= self.dim:
+                    arr[t].factor[d] = None
+                    continue
+                key = (id(f), d)
+                if key not in keep:
+                    x = self.field_points(d)
+                    v = np.array([f(xi) for xi in x], dtype=np.float64) if callable(f) else \
+                        np.ascontiguousarray(f, dtype=np.float64)
+                    if v.shape != x.shape:
+                        raise GdmError("set_coefficient: term %d factor %d has shape %s, field_points(%d) %s"
+                                       % (t, d, v.shape, d, x.shape))
+                    keep[key] = (f, v)
+                arr[t].factor[d] = keep[key][1].ctypes.data
+        check(self.lib.gdm_op_set_coefficient(self.h, len(terms), arr if terms else None), "gdm_op_set_coefficient")
+        self.n_coef_terms = len(terms)
+
+    @property
+    def has_coefficient(self):
+        return getattr(self, "n_coef_terms", 0) > 0
+
+    def coef_tile(self):
+        """(tile_x, tile_y, z_chunk) of the coefficient kernel, kernel axes"""
+        return _capi.coef_tile(self.p, self.dim)
+
+    def coef_solve(self, alpha, tau, rhs_owned, x_owned, rel_tol=1e-8, abs_tol=1e-30, max_it=1000):
+        """x = (alpha M - tau K[kappa])^-1 rhs by CG from the initial guess x,
+        preconditioned by the constant-coefficient direct solve
+        (gdm_coef_solve; system_solve_setup first): returns (iterations,
+        residual)."""
+        self._check_sizes(None, rhs_owned)
+        self._check_sizes(None, x_owned)
+        its, res = ctypes.c_int(0), ctypes.c_double(0.0)
+        check(self.lib.gdm_coef_solve(self.h, float(alpha), float(tau), _ptr(rhs_owned), _ptr(x_owned),
+                                      float(rel_tol), float(abs_tol), int(max_it), ctypes.byref(its),
+                                      ctypes.byref(res)), "gdm_coef_solve")
+        return its.value, res.value
+
     def fastdiag_transform(self, axis, transpose, src_owned, dst_owned):
         """dst = T src along `axis`, T = S (transpose 0) or S^T (1)
         (gdm_fastdiag_transform)"""

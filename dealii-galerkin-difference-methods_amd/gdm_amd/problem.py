@@ -163,13 +163,20 @@ class HeatProblem(WaveProblem):
     S = -K, solved directly (GdmOperator.system_solve(1, h)); h is the
     DiscreteTime step of every step, so a shorter last step needs no new setup.
     scheme "rk": classic RK4 of du/dt = M^-1 (K u + data(t)) through apply +
-    mass_solve_rk."""
+    mass_solve_rk.
 
-    def __init__(self, op, forcing=None, dirichlet=None, scheme="impl"):
+    With a coefficient set on `op` (GdmOperator.set_coefficient) scheme "impl"
+    solves by GdmOperator.coef_solve(1, h) from the previous step's solution
+    with rel_tol / abs_tol / max_it; `iterations` lists the CG counts of the
+    steps taken."""
+
+    def __init__(self, op, forcing=None, dirichlet=None, scheme="impl", rel_tol=1e-8, abs_tol=1e-30, max_it=1000):
         if scheme not in ("impl", "rk"):
             raise GdmError("HeatProblem: scheme is 'impl' or 'rk'")
         WaveProblem.__init__(self, op, forcing, dirichlet)
         self.scheme = scheme
+        self.rel_tol, self.abs_tol, self.max_it = rel_tol, abs_tol, max_it
+        self.iterations = []
         if scheme == "impl":
             op.system_solve_setup()
 
@@ -182,7 +189,11 @@ class HeatProblem(WaveProblem):
                 data.zero_()
                 self.add_data(t + h, data)
                 op.axpby(h, data, 1.0, k)
-            op.system_solve(1.0, h, k, u)
+            if op.has_coefficient:
+                its, _ = op.coef_solve(1.0, h, k, u, self.rel_tol, self.abs_tol, self.max_it)
+                self.iterations.append(its)
+            else:
+                op.system_solve(1.0, h, k, u)
             return
         acc, Y = self._acc[0], self._Y[0]
         stage = u
@@ -195,16 +206,24 @@ class HeatProblem(WaveProblem):
             stage = Y
 
 
-def solve_poisson(op, forcing=None, dirichlet=None, t=0.0):
+def solve_poisson(op, forcing=None, dirichlet=None, t=0.0, rel_tol=1e-8, abs_tol=1e-30, max_it=1000, info=None):
     """The "poisson" simulation type (wave/problem.h:46-71) on an uncut box:
     the device solution of S u = data(t), S = -K of the wave operator `op`
     (created with nitsche > 0: without the box Nitsche terms S is singular),
-    data as in WaveProblem (forcing / dirichlet)."""
+    data as in WaveProblem (forcing / dirichlet).  With a coefficient set on
+    `op` the solve is GdmOperator.coef_solve(0, 1) from a zero guess with
+    rel_tol / abs_tol / max_it; a dict passed as `info` receives "iterations"
+    and "residual"."""
     prob = WaveProblem(op, forcing, dirichlet)
     op.system_solve_setup()
     rhs = prob._kv
     rhs.zero_()
     prob.add_data(t, rhs)
+    if op.has_coefficient:
+        its, res = op.coef_solve(0.0, 1.0, rhs, prob.u, rel_tol, abs_tol, max_it)
+        if info is not None:
+            info["iterations"], info["residual"] = its, res
+        return prob.u
     return op.system_solve(0.0, 1.0, rhs, prob.u)
 
 

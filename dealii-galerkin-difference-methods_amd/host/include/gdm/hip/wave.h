@@ -151,6 +151,51 @@ class StiffnessMatrixOperator {
     check(gdm_system_solve(op, alpha, tau, rhs_owned, x_owned), "gdm_system_solve");
   }
 
+  // A separable coefficient kappa(x) = sum_t k_t0(x_0) ... k_t(dim-1)(x_(dim-1)) > 0
+  // (gdm_op_set_coefficient, after reinit; single rank): every JxW of the
+  // operator part and of the box-face part of compute_rhs is multiplied by
+  // kappa at the quadrature point (stiffness.h:171-181, 296-327).  factors[d]
+  // holds k_td sampled at field_points(d) (nullptr or empty = 1); terms that
+  // pass the same vector object share its tables.  No terms: the constant
+  // operator again.
+  struct CoefTerm {
+    std::array<const std::vector<double> *, dim> factors{};
+  };
+
+  // abscissae at which a factor along direction d is sampled: lo, the Gauss
+  // points cell by cell, hi
+  std::vector<double> field_points(int d) const {
+    const gdm_mesh_desc &m = discretization.get_mesh();
+    std::vector<double> x((std::size_t)m.n_subdivisions[d] * (m.fe_degree + 1) + 2);
+    check(gdm_field_points(&m, d, x.data()), "gdm_field_points");
+    return x;
+  }
+
+  void set_coefficient(const std::vector<CoefTerm> &terms) {
+    std::vector<gdm_coef_term> t(terms.size());
+    for (std::size_t i = 0; i < terms.size(); ++i)
+      for (int d = 0; d < 3; ++d)
+        t[i].factor[d] = d < dim && terms[i].factors[d] && !terms[i].factors[d]->empty() ? terms[i].factors[d]->data()
+                                                                                            : nullptr;
+    check(gdm_op_set_coefficient(op, (int)t.size(), t.data()), "gdm_op_set_coefficient");
+    has_coefficient = !terms.empty();
+  }
+
+  // The solve with a coefficient: CG on alpha M + tau S[kappa] from the initial
+  // guess x, preconditioned by the constant-coefficient direct solve
+  // (setup_system_solve first); SolverCG with ReductionControl(max_it,
+  // abs_tol, rel_tol).  Returns last_step.  Without a coefficient: system_solve.
+  int solve(double alpha, double tau, double *x_owned, const double *rhs_owned, double rel_tol = 1e-8,
+            double abs_tol = 1e-30, int max_it = 1000) const {
+    if (!has_coefficient) {
+      system_solve(alpha, tau, x_owned, rhs_owned);
+      return 0;
+    }
+    int its = 0;
+    check(gdm_coef_solve(op, alpha, tau, rhs_owned, x_owned, rel_tol, abs_tol, max_it, &its, nullptr), "gdm_coef_solve");
+    return its;
+  }
+
   gdm_op *handle() const { return op; }
   const gdm_layout &get_layout() const { return layout; }
   double *owned(VectorType &v) const { return v.get_values() + layout.ghost_planes_below * layout.plane_size; }
@@ -170,11 +215,13 @@ class StiffnessMatrixOperator {
     fq_dev = g_dev = nullptr;
     gdm_op_destroy(op);
     op = nullptr;
+    has_coefficient = false;
   }
 
   const Discretization<dim> &discretization;
   gdm_op *op = nullptr;
   gdm_layout layout{};
+  bool has_coefficient = false;
   // data terms: the functions, their evaluation points and the staging buffers
   Function function_rhs, function_domain_dbc;
   std::vector<double> xq[3], bc_xyz;

@@ -262,6 +262,79 @@ int gdm_field_matrix_1d(const gdm_mesh_desc *mesh, int axis, int which, const do
 int gdm_field_tile(int fe_degree, int *tile_x, int *tile_y, int *z_chunk);
 int gdm_op_set_advection_field(gdm_op *op, int n_terms, const gdm_field_term *terms);
 int gdm_op_set_field_scale(gdm_op *op, const double *s);
+/* ------------------------------------------------------------------------
+ * Separable coefficient of the wave / heat / Poisson operator: kappa(x) = sum
+ * over the terms t of k_t0(x_0) k_t1(x_1) k_t2(x_2) > 0 on a GDM_OP_WAVE
+ * operator (dim 1-3, with or without Nitsche terms) -- compute_rhs of
+ * wave/stiffness.h:151-330 with every JxW(q) of the operator part (:171-181)
+ * and of the box-face part (:296-310) multiplied by kappa at the quadrature
+ * point:
+ *   K[kappa] u = -(kappa grad v, grad u)
+ *                - sum_faces (-<kappa dv/dn, u> - <kappa v, du/dn> + gamma/h_min <kappa v, u>),
+ * data term <gamma/h_min v - dv/dn, kappa g_D> (:312-327).  The source term
+ * and the mass matrix do not change.  Tensor Gauss quadrature factorises this
+ * exactly: per term t and direction d the Kronecker term B_d[k_td] (x)
+ * (M_e[k_te], e != d) with M[f]_ij = sum_q w_q f(x_q) phi_i phi_j and B[f] =
+ * -L[f] - (f(lo) Nitsche end block of row 0 + f(hi) end block of row N - 1),
+ * L[f]_ij = sum_q w_q f(x_q) phi_i' phi_j'.  One kernel launch per apply
+ * (csrc/gdm_vardiff.hip), no face kernel, bitwise repeatable.
+ *
+ *   gdm_coef_matrix_1d   pure host: the band [n_sub + 1][2p+1] of M[f] (which =
+ *                        0) or B[f] (which = 1) the engine uses along `axis`
+ *                        for the Nitsche parameter `nitsche` (gamma; h_min is
+ *                        the mesh's); f sampled at gdm_field_points (NULL: f =
+ *                        1, the band of the constant operator)
+ *   gdm_coef_tile        pure host: the (x, y) tile and the z chunk of the
+ *                        kernel in kernel axes (for tests and sizing)
+ *   gdm_op_set_coefficient
+ *                        builds and uploads every table and all scratch and
+ *                        copies the factor arrays; calling it again replaces
+ *                        the coefficient (it waits for the operator's stream
+ *                        first); n_terms = 0 restores the constant operator
+ *                        and its code path, bit for bit.  factor[d] are HOST
+ *                        arrays sampled at gdm_field_points(d) (NULL = 1;
+ *                        entries d >= dim are ignored); at most
+ *                        GDM_COEF_MAX_TERMS terms; terms that pass the same
+ *                        array (pointer identity) share its tables.
+ *   gdm_coef_solve       x = (alpha M - tau K[kappa])^-1 rhs by CG with
+ *                        ReductionControl(max_it, abs_tol, rel_tol), x the
+ *                        initial guess, preconditioned by the fast
+ *                        diagonalisation of the constant operator with the
+ *                        domain mean of kappa, (alpha M - tau mean(kappa)
+ *                        K_0)^-1 (gdm_system_solve's passes; needs
+ *                        gdm_system_solve_setup).  Poisson: alpha = 0, tau = 1,
+ *                        nitsche > 0; heat-implicit: alpha = 1, tau = dt.
+ *                        *its_host = last_step, *res_host = the last residual
+ *                        norm (either may be NULL).  GDM_ERR_STATE: max_it
+ *                        reached, breakdown (p^T A p <= 0: kappa is not
+ *                        positive), no coefficient set, or before
+ *                        gdm_system_solve_setup.  rhs != x.
+ * While a coefficient is set gdm_apply computes K[kappa] src (bc_values must
+ * be NULL), gdm_time_op works, gdm_add_dirichlet_data uses kappa g (kappa at
+ * the boundary points follows from the samples: Gauss entries in the
+ * tangential directions, the lo / hi entry in the normal one; g_bc is not
+ * modified), gdm_add_load* and the mass entry points are unchanged,
+ * gdm_system_solve returns GDM_ERR_STATE (the direct solve is the
+ * constant-coefficient one: use gdm_coef_solve) and gdm_system_solve_setup
+ * stays legal.  GDM_ERR_UNSUPPORTED: another operator kind, n_ranks > 1, a
+ * periodic mesh, the inner operator of a cut handle, and gdm_apply_planes /
+ * gdm_apply_planes2 while a coefficient is set.  GDM_ERR_ARG: n_terms outside
+ * [0, GDM_COEF_MAX_TERMS], a non-finite sample, and for n_terms = 1 a factor
+ * that vanishes or changes sign.  For sums the caller guarantees kappa > 0.
+ * Separable sums only: a general coefficient is sampled and fitted by a short
+ * separable sum on the caller's side.  Density (a weighted mass) is not
+ * covered.
+ * ---------------------------------------------------------------------- */
+#define GDM_COEF_MAX_TERMS 4
+typedef struct {
+  const double *factor[3]; /* host arrays at gdm_field_points; NULL = 1 */
+} gdm_coef_term;
+int gdm_coef_matrix_1d(const gdm_mesh_desc *mesh, double nitsche, int axis, int which, const double *f,
+                       double *band_host);
+int gdm_coef_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
+int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms);
+int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, double *x, double rel_tol,
+                   double abs_tol, int max_it, int *its_host, double *res_host);
 
 /* dst_owned = M src_local */
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned);
