@@ -26,6 +26,7 @@
 #include "gdm_rk.h"
 #include "gdm_setup.h"
 #include "gdm_vardiff.h"
+#include "gdm_varmass.h"
 #include "gdm_varstencil.h"
 
 namespace {
@@ -222,6 +223,23 @@ struct gdm_op {
     double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, M p
     std::vector<void *> allocations;
   } coef;
+  // separable density of the wave operator (gdm_op_set_density): the launch
+  // plan of gdm_varmass.hip, the domain mean of rho, for one term the two-sweep
+  // line tables of every M_d[r_d] (by kernel axis), for sums W^-1/2 of the
+  // preconditioner, and the CG vectors of gdm_density_solve / gdm_coef_solve,
+  // all device memory allocated when the density is set
+  struct Density {
+    bool active = false;
+    int n_terms = 0;
+    gdmk::VarMassArgs args{};  // src / dst / add / c filled per apply
+    size_t lds = 0;
+    double mean = 1.0;
+    LineTables tab[3];
+    const LineTables *axis_tab[3] = {nullptr, nullptr, nullptr};
+    double *w_isqrt = nullptr;  // [n_owned]: (diag M[rho] / diag M)^-1/2 (n_terms > 1)
+    double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, K p
+    std::vector<void *> allocations;
+  } dens;
   bool cut_inner = false;  // the inner operator of a cut handle
   // load vector / Dirichlet data (gdm_add_load*, gdm_add_dirichlet_data; single
   // rank, non-periodic): shape values times quadrature weights per category,
@@ -262,6 +280,7 @@ void free_op(gdm_op *op) {
   for (void *ptr : op->allocations) (void)hipFree(ptr);
   for (void *ptr : op->field.allocations) (void)hipFree(ptr);
   for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
+  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
   if (op->own_stream) (void)hipStreamDestroy(op->own_stream);
   delete op;
 }
@@ -2150,6 +2169,140 @@ void build_coef(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::Coe
   for (double *&v : nc.cg) v = up(std::vector<double>(n, 0.0));
   nc.active = true;
 }
+
+// ---- separable density of the wave operator (gdm_varmass.hip) ---------------
+
+// dst = M[rho] src (+ c * add)
+void density_apply(gdm_op *op, const double *src, double *dst, const double *add = nullptr, double c = 0.0) {
+  gdmk::VarMassArgs a = op->dens.args;
+  a.src = src;
+  a.dst = dst;
+  a.add = add;
+  a.c = c;
+  hip_check(gdmk::launch_varmass(op->p, a, op->dens.lds, op->stream), "density apply launch");
+}
+
+// M_d[f] of reference direction d, f sampled at gdm_field_points (NULL: 1)
+void density_band(const gdm_mesh_desc *mesh, int d, const double *f, gdm::Band &M) {
+  const unsigned ncell = (unsigned)mesh->n_subdivisions[d];
+  const double h = (mesh->hi[d] - mesh->lo[d]) / ncell;
+  M = gdm::assemble_1d_weighted(mesh->fe_degree, ncell, h, f ? f + 1 : nullptr).M;
+}
+
+// Build the launch plan, tables and scratch of a density into `nd` (every
+// device allocation is recorded in nd.allocations as it is made).
+void build_density(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::Density &nd) {
+  const int p = op->p, W = 2 * p + 1, n1 = p + 1;
+  auto up = [&](const std::vector<double> &h) {
+    double *d = dev_upload(h);
+    nd.allocations.push_back(d);
+    return d;
+  };
+  nd.n_terms = n_terms;
+  // distinct tables: (kernel axis, factor array); terms that pass the same
+  // array share them
+  struct Table {
+    int ax;
+    const double *f;
+    double *dev;
+    gdm::Band B;
+  };
+  std::vector<Table> tabs;
+  auto table = [&](int ax, const double *f) -> size_t {
+    const int d = op->kdir[ax];
+    if (d < 0) f = nullptr;
+    for (size_t i = 0; i < tabs.size(); ++i)
+      if (tabs[i].ax == ax && tabs[i].f == f) return i;
+    gdm::Band B = identity_band(p);
+    if (d >= 0) density_band(&op->mesh, d, f, B);
+    // x: the plain rows; y: zero rows up to a whole tile; z: p zero rows in front and behind
+    const size_t rows = ax == 0 ? B.n : (ax == 1 ? gdmk::varmass_y_rows(B.n) : B.n + 2 * p);
+    std::vector<double> t(rows * W, 0.0);
+    std::copy(B.a.begin(), B.a.end(), t.begin() + (ax == 2 ? (size_t)p * W : 0));
+    tabs.push_back(Table{ax, f, up(t), B});
+    return tabs.size() - 1;
+  };
+  gdmk::VarMassArgs &a = nd.args;
+  a = gdmk::VarMassArgs{};
+  a.Nx = op->K[0];
+  a.Ny = op->K[1];
+  a.Nz = op->K[2];
+  a.n_terms = n_terms;
+  size_t term_tab[gdmk::VMASS_MAX_TERMS][3];
+  for (int t = 0; t < n_terms; ++t) {
+    for (int ax = 0; ax < 3; ++ax)
+      term_tab[t][ax] = table(ax, op->kdir[ax] < 0 ? nullptr : terms[t].factor[op->kdir[ax]]);
+    a.xm[t] = tabs[term_tab[t][0]].dev;
+    a.ym[t] = tabs[term_tab[t][1]].dev;
+    a.zm[t] = tabs[term_tab[t][2]].dev;
+  }
+  nd.lds = gdmk::varmass_lds(p, n_terms);
+  if (nd.lds > 160 * 1024) throw std::runtime_error("density: the launch plan exceeds the LDS of a CU");
+  hip_check(gdmk::varmass_prepare(p, nd.lds), "density: LDS limit");
+
+  // the domain mean: sum_t prod_d mean(r_td), the Gauss weights sum to 1 per cell
+  std::vector<double> xq, wq;
+  gdm::gauss_unit(n1, xq, wq);
+  nd.mean = 0.0;
+  for (int t = 0; t < n_terms; ++t) {
+    double prod = 1.0;
+    for (int d = 0; d < op->dim; ++d) {
+      const double *f = terms[t].factor[d];
+      if (!f) continue;
+      const int ncell = op->mesh.n_subdivisions[d];
+      double s = 0.0;
+      for (int c = 0; c < ncell; ++c)
+        for (int q = 0; q < n1; ++q) s += wq[q] * f[1 + (size_t)c * n1 + q];
+      prod *= s / ncell;
+    }
+    nd.mean += prod;
+  }
+
+  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
+  if (n_terms == 1) {
+    // M[rho]^-1 = (x)_d M_d[r_d]^-1: the two-sweep line tables of every factor;
+    // a negative factor is factored as -M_d[r_d] (the signs multiply to +1)
+    for (int ax = 0; ax < 3; ++ax) {
+      if (op->kdir[ax] < 0) continue;
+      gdm::Band B = tabs[term_tab[0][ax]].B;
+      if (B(0, 0) < 0.0)
+        for (double &v : B.a) v = -v;
+      std::vector<double> lrow, invd;
+      gdm::cholesky_band(B, lrow, invd);
+      lrow.resize(lrow.size() + (size_t)p * (p + 1), 0.0);  // zero pad for the backward sweep
+      nd.tab[ax].lrow = up(lrow);
+      nd.tab[ax].invd = up(invd);
+      nd.axis_tab[ax] = &nd.tab[ax];
+    }
+  } else {
+    // W = diag(M[rho]) / diag(M) = sum_t prod_d diag(M_d[r_td]) / prod_d diag(M_d)
+    std::vector<std::vector<double>> dg((size_t)n_terms * 3);
+    for (int t = 0; t < n_terms; ++t)
+      for (int ax = 0; ax < 3; ++ax) {
+        std::vector<double> &v = dg[(size_t)t * 3 + ax];
+        v.assign((size_t)op->K[ax], 1.0);
+        if (op->kdir[ax] < 0) continue;
+        const gdm::Band &B = tabs[term_tab[t][ax]].B;
+        const gdm::Band M = mesh_mass_1d(&op->mesh, op->kdir[ax]);
+        for (int i = 0; i < op->K[ax]; ++i) v[(size_t)i] = B(i, i) / M(i, i);
+      }
+    std::vector<double> w(n, 1.0);
+    const int Nx = op->K[0], Ny = op->K[1], Nz = op->K[2];
+    if (op->layout.n_owned == (int64_t)Nx * Ny * Nz)
+      for (int z = 0; z < Nz; ++z)
+        for (int y = 0; y < Ny; ++y)
+          for (int x = 0; x < Nx; ++x) {
+            double s = 0.0;
+            for (int t = 0; t < n_terms; ++t)
+              s += dg[(size_t)t * 3][(size_t)x] * dg[(size_t)t * 3 + 1][(size_t)y] * dg[(size_t)t * 3 + 2][(size_t)z];
+            // a density that is not positive is the caller's error: the CG reports the breakdown
+            w[((size_t)z * Ny + y) * Nx + x] = s > 0.0 ? 1.0 / std::sqrt(s) : 1.0;
+          }
+    nd.w_isqrt = up(w);
+  }
+  for (double *&v : nd.cg) v = up(std::vector<double>(n, 0.0));
+  nd.active = true;
+}
 }  // namespace
 
 int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const double *bc_values) {
@@ -2391,6 +2544,178 @@ int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms) 
   for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
   op->coef = std::move(nc);
   return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_density_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (tile_x) *tile_x = gdmk::VMASS_TX;
+  if (tile_y) *tile_y = gdmk::VMASS_TY;
+  if (z_chunk) *z_chunk = gdmk::VMASS_ZC;
+  return GDM_OK;
+}
+
+int gdm_density_cholesky_1d(const gdm_mesh_desc *mesh, int axis, const double *f, double *lrow_host,
+                            double *invd_host) {
+  if (const char *e = host_mesh_error(mesh, axis)) return fail(GDM_ERR_ARG, e);
+  if (!lrow_host || !invd_host) return fail(GDM_ERR_ARG, "NULL argument");
+  if (f) {
+    const size_t n = coef_samples(mesh, axis);
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(f[i])) return fail(GDM_ERR_ARG, "gdm_density_cholesky_1d: a factor sample is not finite");
+  }
+  GDM_GUARD_BEGIN
+  std::vector<double> lrow, invd;
+  try {
+    gdm::Band M;
+    density_band(mesh, axis, f, M);
+    gdm::cholesky_band(M, lrow, invd);
+  } catch (const std::runtime_error &) {
+    return fail(GDM_ERR_ARG, "gdm_density_cholesky_1d: M[f] is not positive definite");
+  }
+  std::copy(lrow.begin(), lrow.end(), lrow_host);
+  std::copy(invd.begin(), invd.end(), invd_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_op_set_density(gdm_op *op, int n_terms, const gdm_coef_term *terms) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: wave operators only");
+  if (op->cut_inner)
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: the cut-cell rows of a cut handle are assembled for the "
+                                     "unit density");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: single rank only");
+  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: not with periodic constraints");
+  if (n_terms < 0 || n_terms > GDM_COEF_MAX_TERMS)
+    return fail(GDM_ERR_ARG, "gdm_op_set_density: n_terms must be in [0, GDM_COEF_MAX_TERMS]");
+  if (n_terms > 0 && !terms) return fail(GDM_ERR_ARG, "gdm_op_set_density: terms is NULL");
+  double sign = 1.0;
+  for (int t = 0; t < n_terms; ++t)
+    for (int d = 0; d < op->dim; ++d) {
+      const double *f = terms[t].factor[d];
+      if (!f) continue;
+      const size_t n = coef_samples(&op->mesh, d);
+      for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(f[i])) return fail(GDM_ERR_ARG, "gdm_op_set_density: a factor sample is not finite");
+        // one term: rho > 0 needs factors that keep their sign and never vanish
+        if (n_terms == 1 && !(f[i] * f[0] > 0.0))
+          return fail(GDM_ERR_ARG, "gdm_op_set_density: a factor of a one-term density vanishes or changes sign");
+      }
+      if (n_terms == 1 && f[0] < 0.0) sign = -sign;
+    }
+  if (sign < 0.0) return fail(GDM_ERR_ARG, "gdm_op_set_density: the one-term density is negative");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  gdm_op::Density nd;
+  if (n_terms > 0) {
+    try {
+      build_density(op, n_terms, terms, nd);
+    } catch (...) {
+      for (void *ptr : nd.allocations) (void)hipFree(ptr);
+      throw;
+    }
+  }
+  // applies in flight read the old tables
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
+  op->dens = std::move(nd);
+  // the pointers into the moved-from object
+  for (int ax = 0; ax < 3; ++ax) op->dens.axis_tab[ax] = op->dens.axis_tab[ax] ? &op->dens.tab[ax] : nullptr;
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_density_apply(gdm_op *op, const double *src, double *dst) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_apply: no density is set (gdm_op_set_density)");
+  if (!src || !dst || src == dst) return fail(GDM_ERR_ARG, "src and dst: distinct device vectors");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  density_apply(op, src, dst);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_density_apply_add(gdm_op *op, const double *src, double c, const double *add, double *dst) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_apply_add: no density is set (gdm_op_set_density)");
+  if (!src || !dst || src == dst || add == dst) return fail(GDM_ERR_ARG, "src, add and dst: distinct device vectors");
+  if (!std::isfinite(c)) return fail(GDM_ERR_ARG, "gdm_density_apply_add: c is not finite");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  density_apply(op, src, dst, add, c);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_density_solve(gdm_op *op, const double *rhs, double *x, double rel_tol, double abs_tol, int max_it,
+                      int *its_host, double *res_host) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_solve: no density is set (gdm_op_set_density)");
+  if (!rhs || !x) return fail(GDM_ERR_ARG, "NULL vector");
+  if (op->dens.n_terms > 1 && rhs == x) return fail(GDM_ERR_ARG, "gdm_density_solve: a sum of terms needs rhs != x");
+  if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const int64_t n = op->layout.n_owned;
+  gdm_op::Density &D = op->dens;
+  if (D.n_terms == 1) {
+    // exact: M[rho]^-1 = (x)_d M_d[r_d]^-1, two-sweep line solves with the weighted factors
+    mass_solve_passes(op, rhs, x, nullptr, nullptr, D.axis_tab);
+    if (its_host) *its_host = 0;
+    if (res_host) *res_host = 0.0;
+    return GDM_OK;
+  }
+  double *r = D.cg[0], *p = D.cg[1], *Ap = D.cg[2], *z = D.cg[3];
+  auto dot = [&](const double *u, const double *v) {
+    double s = 0.0;
+    if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
+    return s;
+  };
+  // z = W^-1/2 M^-1 W^-1/2 r
+  auto precondition = [&](const double *rr, double *zz) {
+    hip_check(gdmk_launch_vmul(n, D.w_isqrt, rr, D.cg[4], op->stream), "scale");
+    mass_solve_passes(op, D.cg[4], D.cg[4], nullptr);
+    hip_check(gdmk_launch_vmul(n, D.w_isqrt, D.cg[4], zz, op->stream), "scale");
+  };
+  // SolverCG with ReductionControl(max_it, abs_tol, rel_tol), x the initial guess
+  density_apply(op, x, r);
+  hip_check(gdmk_launch_axpby(n, 1.0, rhs, -1.0, r, op->stream), "axpby");
+  double res = std::sqrt(dot(r, r));
+  const double tol = std::max(abs_tol, rel_tol * res);
+  int it = 0;
+  auto done = [&](int code, const char *msg) {
+    if (its_host) *its_host = it;
+    if (res_host) *res_host = res;
+    return code == GDM_OK ? GDM_OK : fail(code, msg);
+  };
+  if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_density_solve: the residual is not finite");
+  if (res > tol) {
+    precondition(r, z);
+    hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
+    double rz = dot(r, z);
+    while (true) {
+      if (it >= max_it) return done(GDM_ERR_STATE, "gdm_density_solve: max_it reached (SolverControl::NoConvergence)");
+      ++it;
+      density_apply(op, p, Ap);
+      const double pAp = dot(p, Ap);
+      if (!(pAp > 0.0))
+        return done(GDM_ERR_STATE, "gdm_density_solve: breakdown (p^T M[rho] p <= 0): rho must be positive on the box");
+      const double step = rz / pAp;
+      hip_check(gdmk_launch_axpby(n, step, p, 1.0, x, op->stream), "axpby");
+      hip_check(gdmk_launch_axpby(n, -step, Ap, 1.0, r, op->stream), "axpby");
+      res = std::sqrt(dot(r, r));
+      if (res <= tol) break;
+      if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_density_solve: the residual is not finite");
+      precondition(r, z);
+      const double rz_new = dot(r, z);
+      hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
+      rz = rz_new;
+    }
+  }
+  return done(GDM_OK, "");
   GDM_GUARD_END
 }
 
@@ -3389,7 +3714,9 @@ int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_own
 int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, double *x, double rel_tol, double abs_tol,
                    int max_it, int *its_host, double *res_host) {
   if (int rc = check_fastdiag_op(op, "gdm_coef_solve", false)) return rc;
-  if (!op->coef.active) return fail(GDM_ERR_STATE, "gdm_coef_solve: no coefficient is set (gdm_op_set_coefficient)");
+  const bool dens = op->dens.active;
+  if (!op->coef.active && !dens)
+    return fail(GDM_ERR_STATE, "gdm_coef_solve: no coefficient is set (gdm_op_set_coefficient)");
   if (!op->fd.built) return fail(GDM_ERR_STATE, "gdm_coef_solve: call gdm_system_solve_setup first (the preconditioner)");
   if (!rhs || !x || rhs == x) return fail(GDM_ERR_ARG, "rhs and x: distinct device vectors");
   if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_coef_solve: alpha / tau is not finite");
@@ -3397,8 +3724,11 @@ int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, doub
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
   const int64_t n = op->layout.n_owned;
-  double *r = op->coef.cg[0], *p = op->coef.cg[1], *Ap = op->coef.cg[2], *z = op->coef.cg[3], *Mp = op->coef.cg[4];
-  const double ptau = tau * op->coef.mean;
+  // with a density its own vectors serve (a coefficient need not be set)
+  double *const *cg = dens ? op->dens.cg : op->coef.cg;
+  double *r = cg[0], *p = cg[1], *Ap = cg[2], *z = cg[3], *Mp = cg[4];
+  const double ptau = tau * (op->coef.active ? op->coef.mean : 1.0);
+  const double palpha = alpha * (dens ? op->dens.mean : 1.0);
   auto dot = [&](const double *u, const double *v) {
     double s = 0.0;
     if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
@@ -3406,6 +3736,22 @@ int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, doub
   };
   // dst = (alpha M - tau K[kappa]) src
   auto apply = [&](const double *src, double *dst) {
+    if (dens) {
+      // (alpha M[rho] - tau K) src: K src first, then the weighted mass with the
+      // fused `+ c * add`; K = K_0 (the plain stencil) without a coefficient
+      double *Ks = alpha != 0.0 ? Mp : dst;
+      if (op->coef.active)
+        coef_apply(op, src, Ks);
+      else
+        hip_check(launch_stencil(op, false, src, Ks), "stencil launch");
+      if (alpha != 0.0) {
+        density_apply(op, src, dst, Ks, -tau / alpha);
+        if (alpha != 1.0) hip_check(gdmk_launch_axpby(n, 0.0, src, alpha, dst, op->stream), "axpby");
+      } else {
+        hip_check(gdmk_launch_axpby(n, 0.0, src, -tau, dst, op->stream), "axpby");
+      }
+      return;
+    }
     coef_apply(op, src, dst);
     if (alpha != 0.0) {
       any_stencil(op, true, src, Mp);
@@ -3415,7 +3761,7 @@ int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, doub
     }
   };
   // SolverCG with ReductionControl(max_it, abs_tol, rel_tol), x the initial
-  // guess, preconditioned by (alpha M - tau mean(kappa) K_0)^-1
+  // guess, preconditioned by (alpha mean(rho) M - tau mean(kappa) K_0)^-1 (a mean is 1 where nothing is set)
   apply(x, r);
   hip_check(gdmk_launch_axpby(n, 1.0, rhs, -1.0, r, op->stream), "axpby");
   double res = std::sqrt(dot(r, r));
@@ -3428,7 +3774,7 @@ int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, doub
   };
   if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_coef_solve: the residual is not finite");
   if (res > tol) {
-    if (int rc = fastdiag_solve(op, alpha, ptau, r, z)) return rc;
+    if (int rc = fastdiag_solve(op, palpha, ptau, r, z)) return rc;
     hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
     double rz = dot(r, z);
     while (true) {
@@ -3445,7 +3791,7 @@ int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, doub
       res = std::sqrt(dot(r, r));
       if (res <= tol) break;
       if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_coef_solve: the residual is not finite");
-      if (int rc = fastdiag_solve(op, alpha, ptau, r, z)) return rc;
+      if (int rc = fastdiag_solve(op, palpha, ptau, r, z)) return rc;
       const double rz_new = dot(r, z);
       hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
       rz = rz_new;
@@ -3834,6 +4180,7 @@ int gdm_time_op(gdm_op *op, int which, const double *src, double *dst, const dou
   for (int i = 0; i < n_iter && rc == GDM_OK; ++i) {
     if (which == 0) rc = gdm_apply(op, src, dst, bc_values);
     else if (which == 1) rc = gdm_mass_apply(op, src, dst);
+    else if (which == 3) rc = gdm_density_apply(op, src, dst);
     else rc = gdm_mass_solve(op, src, dst);
   }
   hip_check(hipEventRecord(e1, op->stream), "record");

@@ -165,6 +165,13 @@ def load():
                           ctypes.POINTER(ctypes.c_int)],
         "gdm_op_set_coefficient": [P, i32, P],
         "gdm_coef_solve": [P, d, d, P, P, d, d, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
+        "gdm_density_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                             ctypes.POINTER(ctypes.c_int)],
+        "gdm_density_cholesky_1d": [ctypes.POINTER(MeshDesc), i32, P, P, P],
+        "gdm_op_set_density": [P, i32, P],
+        "gdm_density_apply": [P, P, P],
+        "gdm_density_apply_add": [P, P, d, P, P],
+        "gdm_density_solve": [P, P, P, d, d, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
         "gdm_mass_apply": [P, P, P],
         "gdm_mass_solve": [P, P, P],
         "gdm_mass_solve_rk": [P, P, d, P, P, d, P, P],
@@ -374,6 +381,34 @@ def coef_tile(fe_degree, dim):
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_coef_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_coef_tile")
     return tuple(v.value for v in t)
+
+
+def density_tile(fe_degree, dim):
+    """(tile_x, tile_y, z_chunk) of the density kernel, kernel axes (gdm_density_tile)"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_density_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_density_tile")
+    return tuple(v.value for v in t)
+
+
+def density_cholesky_1d(mesh, axis, f=None):
+    """(lrow [N, p+1], invd [N]): the banded Cholesky rows of the weighted 1D
+    mass matrix M[f] along `axis`; f sampled at field_points (None: f = 1).
+    Pure host, no GPU (gdm_density_cholesky_1d)."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("density_cholesky_1d: axis outside [0, dim)")
+    n, p = mesh.n_subdivisions[axis], mesh.fe_degree
+    fp = None
+    if f is not None:
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.size != n * (p + 1) + 2:
+            raise GdmError("density_cholesky_1d: f has %d samples, field_points has %d" % (f.size, n * (p + 1) + 2))
+        fp = f.ctypes.data_as(ctypes.c_void_p)
+    lrow, invd = np.zeros((n + 1, p + 1)), np.zeros(n + 1)
+    check(load().gdm_density_cholesky_1d(ctypes.byref(mesh), int(axis), fp, lrow.ctypes.data_as(ctypes.c_void_p),
+                                         invd.ctypes.data_as(ctypes.c_void_p)), "gdm_density_cholesky_1d")
+    return lrow, invd
 
 
 def load_vector_1d(mesh, axis, f=None):

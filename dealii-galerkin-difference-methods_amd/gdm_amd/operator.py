@@ -401,15 +401,11 @@ class GdmOperator:
         return x_owned
 
     # -- separable coefficient of the wave / heat / Poisson operator ---------------
-    def set_coefficient(self, terms):
-        """kappa(x) = sum of the terms [k0, k1, k2] of products k0(x_0) k1(x_1)
-        k2(x_2) (gdm_op_set_coefficient; wave operators).  A factor is an array
-        sampled at field_points(axis), a callable evaluated there, or None
-        (= 1).  Terms that pass the same array object share its tables.  An
-        empty list restores the constant operator."""
+    def _coef_terms(self, terms, what):
+        """(ctypes array of gdm_coef_term, the sampled arrays it points into)"""
         terms = [list(t) for t in terms]
         if len(terms) > _capi.COEF_MAX_TERMS:
-            raise GdmError("set_coefficient: at most %d terms" % _capi.COEF_MAX_TERMS)
+            raise GdmError("%s: at most %d terms" % (what, _capi.COEF_MAX_TERMS))
         arr = (_capi.CoefTerm * max(len(terms), 1))()
         keep = {}  # (id(factor object), axis) -> sampled array: object identity becomes pointer identity
         for t, factors in enumerate(terms):
@@ -425,10 +421,20 @@ class GdmOperator:
                     v = np.array([f(xi) for xi in x], dtype=np.float64) if callable(f) else \
                         np.ascontiguousarray(f, dtype=np.float64)
                     if v.shape != x.shape:
-                        raise GdmError("set_coefficient: term %d factor %d has shape %s, field_points(%d) %s"
-                                       % (t, d, v.shape, d, x.shape))
+                        raise GdmError("%s: term %d factor %d has shape %s, field_points(%d) %s"
+                                       % (what, t, d, v.shape, d, x.shape))
                     keep[key] = (f, v)
                 arr[t].factor[d] = keep[key][1].ctypes.data
+        return arr, keep
+
+    def set_coefficient(self, terms):
+        """kappa(x) = sum of the terms [k0, k1, k2] of products k0(x_0) k1(x_1)
+        k2(x_2) (gdm_op_set_coefficient; wave operators).  A factor is an array
+        sampled at field_points(axis), a callable evaluated there, or None
+        (= 1).  Terms that pass the same array object share its tables.  An
+        empty list restores the constant operator."""
+        terms = list(terms)
+        arr, _keep = self._coef_terms(terms, "set_coefficient")
         check(self.lib.gdm_op_set_coefficient(self.h, len(terms), arr if terms else None), "gdm_op_set_coefficient")
         self.n_coef_terms = len(terms)
 
@@ -451,6 +457,50 @@ class GdmOperator:
         check(self.lib.gdm_coef_solve(self.h, float(alpha), float(tau), _ptr(rhs_owned), _ptr(x_owned),
                                       float(rel_tol), float(abs_tol), int(max_it), ctypes.byref(its),
                                       ctypes.byref(res)), "gdm_coef_solve")
+        return its.value, res.value
+
+    # -- separable density: the weighted mass of the wave / heat operator ---------
+    def set_density(self, terms):
+        """rho(x) = sum of the terms [r0, r1, r2] of products r0(x_0) r1(x_1)
+        r2(x_2) > 0 (gdm_op_set_density; wave operators); factors as in
+        set_coefficient.  An empty list removes the density."""
+        terms = list(terms)
+        arr, _keep = self._coef_terms(terms, "set_density")
+        check(self.lib.gdm_op_set_density(self.h, len(terms), arr if terms else None), "gdm_op_set_density")
+        self.n_density_terms = len(terms)
+
+    @property
+    def has_density(self):
+        return getattr(self, "n_density_terms", 0) > 0
+
+    def density_tile(self):
+        """(tile_x, tile_y, z_chunk) of the density kernel, kernel axes"""
+        return _capi.density_tile(self.p, self.dim)
+
+    def density_apply(self, src_owned, dst_owned=None, c=0.0, add=None):
+        """dst = M[rho] src, or with `add` dst = M[rho] src + c * add in the same
+        launch (gdm_density_apply / gdm_density_apply_add)"""
+        if dst_owned is None:
+            dst_owned = self.new_vector(False)
+        self._check_sizes(None, src_owned)
+        self._check_sizes(None, dst_owned)
+        if add is None:
+            check(self.lib.gdm_density_apply(self.h, _ptr(src_owned), _ptr(dst_owned)), "gdm_density_apply")
+        else:
+            self._check_sizes(None, add)
+            check(self.lib.gdm_density_apply_add(self.h, _ptr(src_owned), float(c), _ptr(add), _ptr(dst_owned)),
+                  "gdm_density_apply_add")
+        return dst_owned
+
+    def density_solve(self, rhs_owned, x_owned, rel_tol=1e-8, abs_tol=1e-30, max_it=1000):
+        """x = M[rho]^-1 rhs (gdm_density_solve): one term exact and direct (0
+        iterations, x may be rhs), a sum by preconditioned CG from the initial
+        guess x; returns (iterations, residual)."""
+        self._check_sizes(None, rhs_owned)
+        self._check_sizes(None, x_owned)
+        its, res = ctypes.c_int(0), ctypes.c_double(0.0)
+        check(self.lib.gdm_density_solve(self.h, _ptr(rhs_owned), _ptr(x_owned), float(rel_tol), float(abs_tol),
+                                         int(max_it), ctypes.byref(its), ctypes.byref(res)), "gdm_density_solve")
         return its.value, res.value
 
     def fastdiag_transform(self, axis, transpose, src_owned, dst_owned):

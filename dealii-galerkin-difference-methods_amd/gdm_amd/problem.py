@@ -71,12 +71,20 @@ class WaveProblem:
     built-in g_D (eval_boundary), or a callable t -> device array of
     n_bc_points values in device order (add_dirichlet_data; needs an operator
     with nitsche > 0).  Both are taken at the stage times t + c_s h.  With both
-    None the launches are those of the homogeneous problem."""
+    None the launches are those of the homogeneous problem.
 
-    def __init__(self, op, forcing=None, dirichlet=None):
+    With a density set on `op` (GdmOperator.set_density) the mass is M[rho]:
+    every stage's k comes from GdmOperator.density_solve (direct for one term;
+    a sum by CG from a zero guess with rel_tol / abs_tol / max_it, the counts
+    appended to `iterations`), then rk_update."""
+
+    def __init__(self, op, forcing=None, dirichlet=None, rel_tol=1e-8, abs_tol=1e-30, max_it=1000):
         if op.mesh.n_ranks != 1:
             raise GdmError("WaveProblem: single-rank driver (multi-rank: gdm_amd.distributed)")
         self.op = op
+        self.rel_tol, self.abs_tol, self.max_it = rel_tol, abs_tol, max_it
+        self.iterations = []
+        self._ks = None
         n = op.n_owned
         self.u, self.v = op.new_vector(False), op.new_vector(False)
         self._acc = [op.new_vector(False) for _ in range(2)]
@@ -113,8 +121,24 @@ class WaveProblem:
         """dv/dt = M^-1 compute_rhs(U, t) (wave/problem.h:313-317)"""
         self.op.apply(U, out)
         self.add_data(t, out)
-        self.op.mass_solve(out, out)
+        if self._density():
+            out.copy_(self._density_stage(out))
+        else:
+            self.op.mass_solve(out, out)
         return out
+
+    def _density(self):
+        """whether the operator carries a density (GdmOperator.set_density)"""
+        return getattr(self.op, "has_density", False) is True
+
+    def _density_stage(self, rhs):
+        """k = M[rho]^-1 rhs: direct for one term, else CG from a zero guess"""
+        if self._ks is None:
+            self._ks = self.op.new_vector(False)
+        self._ks.zero_()
+        its, _ = self.op.density_solve(rhs, self._ks, self.rel_tol, self.abs_tol, self.max_it)
+        self.iterations.append(its)
+        return self._ks
 
     def step(self, t, h):
         op, y = self.op, (self.u, self.v)
@@ -135,9 +159,13 @@ class WaveProblem:
             # the v block overwrites Y_v
             op.rk_update(h * RK4_B[s], ku, acc_in[0], acc_out[0], a_next, None if last else y[0],
                          None if last else Y[0])
-            # v block: the mass solve with the update fused into its last pass
-            op.mass_solve_rk(kv, h * RK4_B[s], acc_in[1], acc_out[1], a_next, None if last else y[1],
-                             None if last else Y[1])
+            if self._density():
+                op.rk_update(h * RK4_B[s], self._density_stage(kv), acc_in[1], acc_out[1], a_next,
+                             None if last else y[1], None if last else Y[1])
+            else:
+                # v block: the mass solve with the update fused into its last pass
+                op.mass_solve_rk(kv, h * RK4_B[s], acc_in[1], acc_out[1], a_next, None if last else y[1],
+                                 None if last else Y[1])
             stage = Y
 
     def run(self, start_t, end_t, dt, max_steps=None, callback=None):
@@ -168,28 +196,32 @@ class HeatProblem(WaveProblem):
     With a coefficient set on `op` (GdmOperator.set_coefficient) scheme "impl"
     solves by GdmOperator.coef_solve(1, h) from the previous step's solution
     with rel_tol / abs_tol / max_it; `iterations` lists the CG counts of the
-    steps taken."""
+    steps taken.  With a density set (GdmOperator.set_density) the mass is
+    M[rho]: scheme "impl" takes its right-hand side from density_apply and
+    solves (M[rho] + h S[kappa]) by coef_solve, scheme "rk" takes every stage
+    from density_solve (see WaveProblem)."""
 
     def __init__(self, op, forcing=None, dirichlet=None, scheme="impl", rel_tol=1e-8, abs_tol=1e-30, max_it=1000):
         if scheme not in ("impl", "rk"):
             raise GdmError("HeatProblem: scheme is 'impl' or 'rk'")
-        WaveProblem.__init__(self, op, forcing, dirichlet)
+        WaveProblem.__init__(self, op, forcing, dirichlet, rel_tol, abs_tol, max_it)
         self.scheme = scheme
-        self.rel_tol, self.abs_tol, self.max_it = rel_tol, abs_tol, max_it
-        self.iterations = []
         if scheme == "impl":
             op.system_solve_setup()
 
     def step(self, t, h):
         op, u, k = self.op, self.u, self._kv
         if self.scheme == "impl":
-            op.mass_apply(u, k)
+            if self._density():
+                op.density_apply(u, k)
+            else:
+                op.mass_apply(u, k)
             if self.forcing is not None or self.dirichlet is not None:
                 data = self._Y[0]
                 data.zero_()
                 self.add_data(t + h, data)
                 op.axpby(h, data, 1.0, k)
-            if op.has_coefficient:
+            if op.has_coefficient or self._density():
                 its, _ = op.coef_solve(1.0, h, k, u, self.rel_tol, self.abs_tol, self.max_it)
                 self.iterations.append(its)
             else:
@@ -201,8 +233,12 @@ class HeatProblem(WaveProblem):
             op.apply(stage, k)
             self.add_data(t + RK4_C[s] * h, k)
             last = s == 3
-            op.mass_solve_rk(k, h * RK4_B[s], u if s == 0 else acc, u if last else acc,
+            if self._density():
+                op.rk_update(h * RK4_B[s], self._density_stage(k), u if s == 0 else acc, u if last else acc,
                              0.0 if last else h * RK4_A[s], None if last else u, None if last else Y)
+            else:
+                op.mass_solve_rk(k, h * RK4_B[s], u if s == 0 else acc, u if last else acc,
+                                 0.0 if last else h * RK4_A[s], None if last else u, None if last else Y)
             stage = Y
 
 

@@ -185,14 +185,46 @@ class StiffnessMatrixOperator {
   // guess x, preconditioned by the constant-coefficient direct solve
   // (setup_system_solve first); SolverCG with ReductionControl(max_it,
   // abs_tol, rel_tol).  Returns last_step.  Without a coefficient: system_solve.
+  // With a density the system is alpha M[rho] + tau S[kappa] (with or without
+  // a coefficient).
   int solve(double alpha, double tau, double *x_owned, const double *rhs_owned, double rel_tol = 1e-8,
             double abs_tol = 1e-30, int max_it = 1000) const {
-    if (!has_coefficient) {
+    if (!has_coefficient && !has_density) {
       system_solve(alpha, tau, x_owned, rhs_owned);
       return 0;
     }
     int its = 0;
     check(gdm_coef_solve(op, alpha, tau, rhs_owned, x_owned, rel_tol, abs_tol, max_it, &its, nullptr), "gdm_coef_solve");
+    return its;
+  }
+
+  // A separable density rho(x) = sum_t r_t0(x_0) ... r_t(dim-1)(x_(dim-1)) > 0
+  // (gdm_op_set_density, after reinit; single rank): the mass matrix with
+  // every JxW multiplied by rho at the quadrature point (mass.h:47-249), terms
+  // as in set_coefficient.  No terms: the unit density again.
+  void set_density(const std::vector<CoefTerm> &terms) {
+    std::vector<gdm_coef_term> t(terms.size());
+    for (std::size_t i = 0; i < terms.size(); ++i)
+      for (int d = 0; d < 3; ++d)
+        t[i].factor[d] = d < dim && terms[i].factors[d] && !terms[i].factors[d]->empty() ? terms[i].factors[d]->data()
+                                                                                            : nullptr;
+    check(gdm_op_set_density(op, (int)t.size(), t.data()), "gdm_op_set_density");
+    has_density = !terms.empty();
+  }
+
+  // dst = M[rho] src (distinct device vectors)
+  void density_apply(double *dst_owned, const double *src_owned) const {
+    check(gdm_density_apply(op, src_owned, dst_owned), "gdm_density_apply");
+  }
+
+  // x = M[rho]^-1 rhs: one term exact and direct (returns 0; x may be rhs), a
+  // sum by CG from the initial guess x with ReductionControl(max_it, abs_tol,
+  // rel_tol), preconditioned by the diagonally scaled exact mass inverse.
+  // Returns last_step.
+  int density_solve(double *x_owned, const double *rhs_owned, double rel_tol = 1e-8, double abs_tol = 1e-30,
+                    int max_it = 1000) const {
+    int its = 0;
+    check(gdm_density_solve(op, rhs_owned, x_owned, rel_tol, abs_tol, max_it, &its, nullptr), "gdm_density_solve");
     return its;
   }
 
@@ -216,12 +248,13 @@ class StiffnessMatrixOperator {
     gdm_op_destroy(op);
     op = nullptr;
     has_coefficient = false;
+    has_density = false;
   }
 
   const Discretization<dim> &discretization;
   gdm_op *op = nullptr;
   gdm_layout layout{};
-  bool has_coefficient = false;
+  bool has_coefficient = false, has_density = false;
   // data terms: the functions, their evaluation points and the staging buffers
   Function function_rhs, function_domain_dbc;
   std::vector<double> xq[3], bc_xyz;

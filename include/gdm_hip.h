@@ -322,8 +322,8 @@ int gdm_op_set_field_scale(gdm_op *op, const double *s);
  * [0, GDM_COEF_MAX_TERMS], a non-finite sample, and for n_terms = 1 a factor
  * that vanishes or changes sign.  For sums the caller guarantees kappa > 0.
  * Separable sums only: a general coefficient is sampled and fitted by a short
- * separable sum on the caller's side.  Density (a weighted mass) is not
- * covered.
+ * separable sum on the caller's side.  The density (a weighted mass) is set
+ * by gdm_op_set_density below.
  * ---------------------------------------------------------------------- */
 #define GDM_COEF_MAX_TERMS 4
 typedef struct {
@@ -335,6 +335,69 @@ int gdm_coef_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk
 int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms);
 int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, double *x, double rel_tol,
                    double abs_tol, int max_it, int *its_host, double *res_host);
+
+/* ------------------------------------------------------------------------
+ * Separable density of the wave / heat operator: rho(x) = sum over the terms t
+ * of r_t0(x_0) r_t1(x_1) r_t2(x_2) > 0 on a GDM_OP_WAVE operator, for
+ *   rho u_tt = div(kappa grad u) + f    and    rho c u_t = div(kappa grad u) + f.
+ * The weighted mass is M[rho]_ij = sum_q w_q rho(x_q) phi_i phi_j: the cell loop
+ * of wave/mass.h:47-249 with every JxW(q) multiplied by rho at the quadrature
+ * point.  Tensor Gauss quadrature factorises it exactly, M[rho] = sum_t
+ * (x)_d M_d[r_td] with the bands of gdm_coef_matrix_1d(which = 0).  The terms
+ * are gdm_coef_term: HOST arrays sampled at gdm_field_points(d) (NULL = 1;
+ * entries d >= dim are ignored), at most GDM_COEF_MAX_TERMS terms, terms that
+ * pass the same array (pointer identity) share its tables.
+ *
+ *   gdm_density_tile     pure host: the (x, y) tile and the z chunk of the
+ *                        kernel (csrc/gdm_varmass.hip) in kernel axes
+ *   gdm_density_cholesky_1d
+ *                        pure host: the row-form banded Cholesky factor of
+ *                        M_axis[f] in the layout of gdm_mass_cholesky_1d
+ *                        (lrow [N][p+1], invd [N]); GDM_ERR_ARG when M[f] is not
+ *                        positive definite
+ *   gdm_op_set_density   builds and uploads every table and all scratch and
+ *                        copies what it needs of the factor arrays; calling it
+ *                        again replaces the density (it waits for the
+ *                        operator's stream first); n_terms = 0 removes it.
+ *   gdm_density_apply    dst = M[rho] src, one kernel launch, bitwise
+ *                        repeatable (src != dst)
+ *   gdm_density_apply_add
+ *                        dst = M[rho] src + c * add in the same launch (add !=
+ *                        dst; add may be NULL: the plain apply)
+ *   gdm_density_solve    x = M[rho]^-1 rhs.  One term: exact and direct,
+ *                        (x)_d M_d[r_d]^-1 by two-sweep line solves with the
+ *                        weighted Cholesky factors; *its_host = 0, the
+ *                        tolerances are not read, x = rhs is allowed.  A sum:
+ *                        CG with ReductionControl(max_it, abs_tol, rel_tol), x
+ *                        the initial guess (rhs != x), preconditioned by
+ *                        W^-1/2 M^-1 W^-1/2 with W = diag(M[rho]) / diag(M) and
+ *                        the exact passes of gdm_mass_solve.  *its_host =
+ *                        last_step, *res_host = the last residual norm (either
+ *                        may be NULL).  GDM_ERR_STATE: no density set, max_it
+ *                        reached, breakdown (p^T M[rho] p <= 0: rho is not
+ *                        positive).
+ * With a density set gdm_coef_solve solves (alpha M[rho] - tau K[kappa]) x =
+ * rhs, with or without a coefficient (none: K[kappa] = K_0), preconditioned by
+ * the fast diagonalisation of (alpha mean(rho) M - tau mean(kappa) K_0); the
+ * means are Gauss-weighted.  gdm_time_op(which = 3) times gdm_density_apply.
+ * Nothing else changes: gdm_apply, gdm_mass_apply, gdm_mass_solve* and
+ * gdm_system_solve keep computing with the unweighted M (it is also part of the
+ * preconditioners), bit for bit.  GDM_ERR_UNSUPPORTED: another operator kind,
+ * n_ranks > 1, a periodic mesh, the inner operator of a cut handle.
+ * GDM_ERR_ARG: n_terms outside [0, GDM_COEF_MAX_TERMS], a non-finite sample,
+ * and for n_terms = 1 a factor that vanishes or changes sign (or a negative
+ * product).  For sums the caller guarantees rho > 0.  Not covered: a density
+ * on periodic, multi-rank or cut meshes, a time-dependent density, and an RK
+ * update fused into the weighted solve.
+ * ---------------------------------------------------------------------- */
+int gdm_density_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
+int gdm_density_cholesky_1d(const gdm_mesh_desc *mesh, int axis, const double *f, double *lrow_host,
+                            double *invd_host);
+int gdm_op_set_density(gdm_op *op, int n_terms, const gdm_coef_term *terms);
+int gdm_density_apply(gdm_op *op, const double *src, double *dst);
+int gdm_density_apply_add(gdm_op *op, const double *src, double c, const double *add, double *dst);
+int gdm_density_solve(gdm_op *op, const double *rhs, double *x, double rel_tol, double abs_tol, int max_it,
+                      int *its_host, double *res_host);
 
 /* dst_owned = M src_local */
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned);
@@ -822,7 +885,8 @@ int gdm_bc_points(const gdm_op *op, double *xyz_host);
 int gdm_bc_reference_order(const gdm_op *op, int64_t *ref_to_dev_host);
 
 /* time n_iter back-to-back applications with HIP events on the operator's
- * stream; which: 0 = gdm_apply, 1 = gdm_mass_apply, 2 = gdm_mass_solve.
+ * stream; which: 0 = gdm_apply, 1 = gdm_mass_apply, 2 = gdm_mass_solve, 3 =
+ * gdm_density_apply (bc_values unused).
  * avg_ms_host receives the mean time per application. */
 int gdm_time_op(gdm_op *op, int which, const double *src, double *dst, const double *bc_values, int n_iter,
                 double *avg_ms_host);
