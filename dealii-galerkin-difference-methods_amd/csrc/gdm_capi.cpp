@@ -17,6 +17,7 @@
 
 #include "../../include/gdm_hip.h"
 #include "gdm_coeffs.h"
+#include "gdm_coefgrid.h"
 #include "gdm_kernels.h"
 #include "gdm_load.h"
 #include "gdm_elasticity.h"
@@ -221,6 +222,12 @@ struct gdm_op {
     double *kappa_bc = nullptr, *g_scaled = nullptr;  // [n_bc_points]
     double mean = 1.0;
     double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, M p
+    // general coefficient on the Gauss grid (gdm_op_set_coefficient_grid): the
+    // launch plan of gdm_coefgrid.hip; kq and kappa_bc are the caller's arrays
+    bool grid = false;
+    gdmk::CgArgs grid_args{};  // src / dst filled per apply
+    std::vector<gdmk::CgFace> grid_faces;
+    double *face_scratch = nullptr;  // [2][largest face's Gauss points]
     std::vector<void *> allocations;
   } coef;
   // separable density of the wave operator (gdm_op_set_density): the launch
@@ -2059,6 +2066,17 @@ const char *kCoefPlanes = "gdm_apply_planes: not with a separable coefficient (g
 // ---- separable coefficient of the wave operator (gdm_vardiff.hip) -----------
 
 void coef_apply(gdm_op *op, const double *src, double *dst) {
+  if (op->coef.grid) {
+    gdmk::CgArgs g = op->coef.grid_args;
+    g.src = src;
+    g.dst = dst;
+    hip_check(gdmk::launch_cg(op->p, g, op->stream), "grid coefficient apply launch");
+    // the box faces one after the other: they share the edge and corner columns and the scratch
+    for (const gdmk::CgFace &F : op->coef.grid_faces)
+      hip_check(gdmk_cg_face(F, src, op->coef.kappa_bc, op->coef.face_scratch, dst, op->stream),
+                "grid coefficient face launch");
+    return;
+  }
   gdmk::DiffArgs a = op->coef.args;
   a.src = src;
   a.dst = dst;
@@ -2168,6 +2186,178 @@ void build_coef(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::Coe
   const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
   for (double *&v : nc.cg) v = up(std::vector<double>(n, 0.0));
   nc.active = true;
+}
+
+// ---- general coefficient on the Gauss grid (gdm_coefgrid.hip) ---------------
+
+// the kernel's tables of one direction: per Gauss point the first node of the
+// cell's DoF box, the p + 1 basis values and physical derivatives, w_q h
+struct CoefGridTables {
+  std::vector<int32_t> first;
+  std::vector<double> val, der, w;
+};
+void coef_grid_tables(int p, unsigned ncell, double h, CoefGridTables &T) {
+  const int n1 = p + 1;
+  std::vector<double> xq, wq;
+  gdm::gauss_unit(n1, xq, wq);
+  const size_t Q = (size_t)ncell * n1;
+  T.first.resize(Q);
+  T.w.resize(Q);
+  T.val.resize(Q * n1);
+  T.der.resize(Q * n1);
+  for (unsigned c = 0; c < ncell; ++c) {
+    const int cat = (int)gdm::category(c, (unsigned)p, ncell), off = (int)gdm::box_offset(c, (unsigned)p, ncell);
+    for (int q = 0; q < n1; ++q) {
+      const size_t g = (size_t)c * n1 + q;
+      T.first[g] = off;
+      T.w[g] = wq[q] * h;
+      for (int i = 0; i < n1; ++i) {
+        T.val[g * n1 + i] = gdm::shape_1d(p, cat, i, xq[q], 0);
+        T.der[g * n1 + i] = gdm::shape_1d(p, cat, i, xq[q], 1) / h;
+      }
+    }
+  }
+}
+
+// Build the launch plan, tables and scratch of a grid coefficient into `nc`,
+// and run the reduction over kq (and kbc): false = a sample is not finite or
+// not positive.
+bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Coef &nc) {
+  const int p = op->p, n1 = p + 1;
+  auto up = [&](const auto &h) {
+    auto *d = dev_upload(h);
+    nc.allocations.push_back((void *)d);
+    return d;
+  };
+  nc.grid = true;
+  gdmk::CgArgs &a = nc.grid_args;
+  a = gdmk::CgArgs{};
+  a.kq = kq;
+  double volume = 1.0;
+  for (int k = 0; k < 3; ++k) {
+    const int d = op->kdir[k];
+    CoefGridTables T;
+    int N = 1;
+    if (d < 0) {
+      T.first.assign(1, 0);
+      T.w.assign(1, 1.0);
+      T.val.assign((size_t)n1, 0.0);
+      T.der.assign((size_t)n1, 0.0);
+      T.val[0] = 1.0;
+    } else {
+      const unsigned ncell = (unsigned)op->mesh.n_subdivisions[d];
+      coef_grid_tables(p, ncell, (op->mesh.hi[d] - op->mesh.lo[d]) / ncell, T);
+      N = op->N[d];
+      volume *= op->mesh.hi[d] - op->mesh.lo[d];
+    }
+    const int Q = (int)T.first.size();
+    // the Gauss points whose box holds node i: a contiguous range (the boxes move monotonically)
+    std::vector<int32_t> qlo((size_t)N, Q), qhi((size_t)N, 0);
+    for (int q = 0; q < Q; ++q)
+      for (int i = T.first[q]; i <= std::min(N - 1, T.first[q] + p); ++i) {
+        qlo[(size_t)i] = std::min(qlo[(size_t)i], q);
+        qhi[(size_t)i] = std::max(qhi[(size_t)i], q + 1);
+      }
+    // the kernel's compile-time bounds on a tile's footprint
+    const int tile = k == 0 ? gdmk::cg_tx(p) : gdmk::cg_ty(p);
+    for (int i0 = 0; i0 < N && k < 2; i0 += tile) {
+      const int il = std::min(N, i0 + tile) - 1;
+      const int q0 = qlo[(size_t)i0], q1 = qhi[(size_t)il];
+      const int span = std::min(T.first[(size_t)q1 - 1] + p, N - 1) - T.first[(size_t)q0] + 1;
+      if (q1 <= q0 || q1 - q0 > (k == 0 ? gdmk::cg_nqx(p) : gdmk::cg_nqy(p)) ||
+          span > (k == 0 ? gdmk::cg_sx(p) : gdmk::cg_sy(p)))
+        throw std::runtime_error("grid coefficient: a tile's footprint exceeds the kernel's bounds");
+    }
+    gdmk::CgAxis &A = a.ax[k];
+    A.N = N;
+    A.Q = Q;
+    A.first = up(T.first);
+    A.val = up(T.val);
+    A.der = up(T.der);
+    A.w = up(T.w);
+    A.qlo = up(qlo);
+    A.qhi = up(qhi);
+  }
+  hip_check(gdmk::cg_prepare(p), "grid coefficient: LDS limit");
+
+  // the box faces (Nitsche part)
+  const int64_t nbc = op->layout.n_bc_points;
+  int64_t max_face = 1;
+  if (op->nitsche > 0.0) {
+    const int64_t stride[3] = {1, op->N[0], (int64_t)op->N[0] * op->N[1]};
+    auto axis_of = [&](int e) {  // kernel axis of reference direction e (-1: any trivial axis)
+      for (int k = 0; k < 3; ++k)
+        if (op->kdir[k] == e) return k;
+      throw std::runtime_error("grid coefficient: direction without a kernel axis");
+    };
+    for (const Face &F : op->faces) {
+      gdmk::CgFace f{};
+      const gdmk::CgAxis &A0 = a.ax[axis_of(F.t0.dim_index)], &A1 = a.ax[axis_of(F.t1.dim_index)];
+      f.n0 = F.t0.n_nodes;
+      f.n1 = F.t1.n_nodes;
+      f.Q0 = F.t0.Q;
+      f.Q1 = F.t1.Q;
+      f.nk = n1;
+      f.first0 = A0.first;
+      f.val0 = A0.val;
+      f.first1 = A1.first;
+      f.val1 = A1.val;
+      f.qs0 = F.t0.qs;
+      f.qc0 = F.t0.qc;
+      f.w0 = F.t0.w;
+      f.wmax0 = F.t0.wmax;
+      f.qs1 = F.t1.qs;
+      f.qc1 = F.t1.qc;
+      f.w1 = F.t1.w;
+      f.wmax1 = F.t1.wmax;
+      f.stride0 = F.t0.stride;
+      f.stride1 = F.t1.stride;
+      f.stride_d = stride[F.d];
+      f.base = (F.side ? (int64_t)(op->N[F.d] - 1 - p) : 0) * stride[F.d];
+      f.goff = F.offset;
+      f.gamma = nitsche_over_hmin(&op->mesh, op->nitsche);
+      const unsigned ncd = (unsigned)op->mesh.n_subdivisions[F.d];
+      const double hd = (op->mesh.hi[F.d] - op->mesh.lo[F.d]) / ncd;
+      const int cat = F.side ? (int)gdm::category(ncd - 1, (unsigned)p, ncd) : 0;
+      const double xs = F.side ? 1.0 : 0.0, nrm = F.side ? 1.0 : -1.0;
+      for (int k = 0; k < n1; ++k) {
+        f.tr[k] = gdm::shape_1d(p, cat, k, xs, 0);
+        f.dk[k] = nrm * gdm::shape_1d(p, cat, k, xs, 1) / hd;
+      }
+      if (f.Q0 != A0.Q || f.Q1 != A1.Q || f.n0 != A0.N || f.n1 != A1.N)
+        throw std::runtime_error("grid coefficient: face and volume tables disagree");
+      max_face = std::max(max_face, (int64_t)f.Q0 * f.Q1);
+      nc.grid_faces.push_back(f);
+    }
+    nc.kappa_bc = const_cast<double *>(kbc);  // borrowed, read only
+    nc.g_scaled = up(std::vector<double>((size_t)std::max<int64_t>(nbc, 1), 0.0));
+    nc.face_scratch = up(std::vector<double>((size_t)(2 * max_face), 0.0));
+  }
+  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
+  for (double *&v : nc.cg) v = up(std::vector<double>(n, 0.0));
+
+  // one reduction over kq (and kbc): the Gauss-weighted mean, and the samples that are not finite or not positive
+  constexpr int blocks = 1024;
+  std::vector<gdmk::CgAxis> axes(a.ax, a.ax + 3);
+  const gdmk::CgAxis *axes_dev = up(axes);
+  double *part = up(std::vector<double>((size_t)4 * blocks, 0.0));
+  const int64_t nq = (int64_t)a.ax[0].Q * a.ax[1].Q * a.ax[2].Q;
+  hip_check(gdmk_cg_reduce(kq, nq, axes_dev, part, part + blocks, blocks, op->stream), "grid coefficient reduction");
+  const bool faces = op->nitsche > 0.0 && nbc > 0;
+  if (faces)
+    hip_check(gdmk_cg_reduce(kbc, nbc, nullptr, part + 2 * blocks, part + 3 * blocks, blocks, op->stream),
+              "grid coefficient reduction");
+  std::vector<double> host((size_t)4 * blocks);
+  hip_check(hipMemcpyAsync(host.data(), part, sizeof(double) * host.size(), hipMemcpyDeviceToHost, op->stream), "copy");
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  double sum = 0.0, bad = 0.0;
+  for (int b = 0; b < blocks; ++b) {
+    sum += host[(size_t)b];
+    bad += host[(size_t)blocks + b] + host[(size_t)3 * blocks + b];
+  }
+  nc.mean = sum / volume;
+  nc.active = true;
+  return bad == 0.0;
 }
 
 // ---- separable density of the wave operator (gdm_varmass.hip) ---------------
@@ -2537,6 +2727,65 @@ int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms) 
     } catch (...) {
       for (void *ptr : nc.allocations) (void)hipFree(ptr);
       throw;
+    }
+  }
+  // applies in flight read the old tables
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
+  op->coef = std::move(nc);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_coef_grid_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (tile_x) *tile_x = gdmk::cg_tx(fe_degree);
+  if (tile_y) *tile_y = gdmk::cg_ty(fe_degree);
+  if (z_chunk) *z_chunk = gdmk::cg_zc(fe_degree);
+  return GDM_OK;
+}
+
+int gdm_coef_grid_tables_1d(const gdm_mesh_desc *mesh, int axis, double *val_host, double *der_host,
+                            int32_t *first_host) {
+  if (int rc = check_field_mesh(mesh, axis)) return rc;
+  if (!val_host || !der_host || !first_host) return fail(GDM_ERR_ARG, "NULL argument");
+  GDM_GUARD_BEGIN
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  CoefGridTables T;
+  coef_grid_tables(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc, T);
+  std::copy(T.val.begin(), T.val.end(), val_host);
+  std::copy(T.der.begin(), T.der.end(), der_host);
+  std::copy(T.first.begin(), T.first.end(), first_host);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_op_set_coefficient_grid(gdm_op *op, const double *kq, const double *kbc) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: wave operators only");
+  if (op->cut_inner)
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: the cut-cell rows of a cut handle are assembled "
+                                     "for the constant coefficient");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: single rank only");
+  if (op->mesh.periodic)
+    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: not with periodic constraints");
+  if (kq && op->nitsche > 0.0 && op->layout.n_bc_points > 0 && !kbc)
+    return fail(GDM_ERR_ARG, "gdm_op_set_coefficient_grid: an operator with nitsche > 0 needs kbc");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  gdm_op::Coef nc;
+  bool ok = true;
+  if (kq) {
+    try {
+      ok = build_coef_grid(op, kq, kbc, nc);
+    } catch (...) {
+      for (void *ptr : nc.allocations) (void)hipFree(ptr);
+      throw;
+    }
+    if (!ok) {
+      for (void *ptr : nc.allocations) (void)hipFree(ptr);
+      return fail(GDM_ERR_ARG, "gdm_op_set_coefficient_grid: a sample of kappa is not finite or not positive");
     }
   }
   // applies in flight read the old tables

@@ -165,6 +165,10 @@ def load():
                           ctypes.POINTER(ctypes.c_int)],
         "gdm_op_set_coefficient": [P, i32, P],
         "gdm_coef_solve": [P, d, d, P, P, d, d, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
+        "gdm_op_set_coefficient_grid": [P, P, P],
+        "gdm_coef_grid_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                               ctypes.POINTER(ctypes.c_int)],
+        "gdm_coef_grid_tables_1d": [ctypes.POINTER(MeshDesc), i32, P, P, P],
         "gdm_density_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                              ctypes.POINTER(ctypes.c_int)],
         "gdm_density_cholesky_1d": [ctypes.POINTER(MeshDesc), i32, P, P, P],
@@ -381,6 +385,31 @@ def coef_tile(fe_degree, dim):
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_coef_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_coef_tile")
     return tuple(v.value for v in t)
+
+
+def coef_grid_tile(fe_degree, dim):
+    """(tile_x, tile_y, z_chunk) of the grid coefficient kernel, kernel axes (gdm_coef_grid_tile)"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_coef_grid_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_coef_grid_tile")
+    return tuple(v.value for v in t)
+
+
+def coef_grid_tables_1d(mesh, axis):
+    """(val[Q][p+1], der[Q][p+1], first[Q]) of the grid coefficient kernel along
+    `axis`, Q = n_sub (p+1): basis values, physical derivatives and the first
+    node of the cell's DoF box per Gauss point (gdm_coef_grid_tables_1d).  Pure
+    host, no GPU."""
+    import numpy as np
+
+    if not 0 <= axis < mesh.dim:
+        raise GdmError("coef_grid_tables_1d: axis outside [0, dim)")
+    n1 = mesh.fe_degree + 1
+    Q = mesh.n_subdivisions[axis] * n1
+    val, der, first = np.zeros((Q, n1)), np.zeros((Q, n1)), np.zeros(Q, dtype=np.int32)
+    check(load().gdm_coef_grid_tables_1d(ctypes.byref(mesh), int(axis), val.ctypes.data_as(ctypes.c_void_p),
+                                         der.ctypes.data_as(ctypes.c_void_p),
+                                         first.ctypes.data_as(ctypes.c_void_p)), "gdm_coef_grid_tables_1d")
+    return val, der, first
 
 
 def density_tile(fe_degree, dim):

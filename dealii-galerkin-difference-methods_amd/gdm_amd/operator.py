@@ -437,10 +437,58 @@ class GdmOperator:
         arr, _keep = self._coef_terms(terms, "set_coefficient")
         check(self.lib.gdm_op_set_coefficient(self.h, len(terms), arr if terms else None), "gdm_op_set_coefficient")
         self.n_coef_terms = len(terms)
+        self._coef_grid = None  # a separable coefficient replaces a grid one
+
+    def set_coefficient_grid(self, kq, kbc=None):
+        """A general kappa > 0 sampled on the tensor Gauss grid
+        (gdm_op_set_coefficient_grid; wave operators).  kq is a device tensor
+        in add_load's layout kq[(qz Q_y + qy) Q_x + qx] (quadrature_points()),
+        kbc a device tensor of kappa at bc_points() (needed with nitsche > 0);
+        the engine borrows both, the operator keeps the references, and values
+        overwritten in place are seen by the next apply.  kq may also be a
+        callable kappa(x), x of shape (n, 3): it is evaluated on the host at
+        the Gauss grid and at bc_points() and uploaded.  None removes the
+        coefficient."""
+        if kq is None:
+            check(self.lib.gdm_op_set_coefficient_grid(self.h, None, None), "gdm_op_set_coefficient_grid")
+            self._coef_grid = None
+            self.n_coef_terms = 0
+            return
+        torch = self._torch
+        dev = "cuda:%d" % self.device
+        if callable(kq):
+            kappa = kq
+            xq = self.quadrature_points() + [np.zeros(1)] * (3 - self.dim)
+            x = np.zeros((xq[2].size, xq[1].size, xq[0].size, 3))
+            x[..., 0] = xq[0][None, None, :]
+            x[..., 1] = xq[1][None, :, None]
+            x[..., 2] = xq[2][:, None, None]
+            kq = torch.from_numpy(np.ascontiguousarray(kappa(x.reshape(-1, 3)), dtype=np.float64)).to(dev)
+            if self.n_bc_points > 0:  # ignored by an operator without Nitsche terms
+                kbc = torch.from_numpy(np.ascontiguousarray(kappa(self.bc_points()), dtype=np.float64)).to(dev)
+        nq = 1
+        for d in range(self.dim):
+            nq *= self.mesh.n_subdivisions[d] * (self.p + 1)
+        if kq.numel() != nq:
+            raise GdmError("set_coefficient_grid: kq has %d entries, the quadrature grid %d" % (kq.numel(), nq))
+        if kbc is not None and kbc.numel() != self.n_bc_points:
+            raise GdmError("set_coefficient_grid: kbc has %d entries, expected %d" % (kbc.numel(), self.n_bc_points))
+        check(self.lib.gdm_op_set_coefficient_grid(self.h, _ptr(kq), _ptr(kbc)), "gdm_op_set_coefficient_grid")
+        self._coef_grid = (kq, kbc)  # keeps the borrowed memory alive
+        self.n_coef_terms = 0
 
     @property
     def has_coefficient(self):
-        return getattr(self, "n_coef_terms", 0) > 0
+        return getattr(self, "n_coef_terms", 0) > 0 or getattr(self, "_coef_grid", None) is not None
+
+    def coef_grid_tile(self):
+        """(tile_x, tile_y, z_chunk) of the grid coefficient kernel, kernel axes"""
+        return _capi.coef_grid_tile(self.p, self.dim)
+
+    def coef_grid_tables_1d(self, axis):
+        """(val[Q][p+1], der[Q][p+1], first[Q]) of the grid coefficient kernel
+        along `axis` (gdm_coef_grid_tables_1d)"""
+        return _capi.coef_grid_tables_1d(self.mesh, axis)
 
     def coef_tile(self):
         """(tile_x, tile_y, z_chunk) of the coefficient kernel, kernel axes"""

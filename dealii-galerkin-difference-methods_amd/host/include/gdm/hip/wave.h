@@ -181,6 +181,18 @@ class StiffnessMatrixOperator {
     has_coefficient = !terms.empty();
   }
 
+  // A general coefficient kappa > 0 on the tensor Gauss grid
+  // (gdm_op_set_coefficient_grid, after reinit; single rank): kq_dev holds
+  // kappa at the Gauss points in the layout of the source term's grid,
+  // kq[(qz Q_y + qy) Q_x + qx], kbc_dev kappa at the boundary points in the
+  // engine's block(0) order (needed with nitsche > 0).  Both are DEVICE arrays
+  // the engine borrows: they must outlive the coefficient and may be
+  // overwritten in place between applies.  nullptr: the constant operator again.
+  void set_coefficient_grid(const double *kq_dev, const double *kbc_dev) {
+    check(gdm_op_set_coefficient_grid(op, kq_dev, kbc_dev), "gdm_op_set_coefficient_grid");
+    has_coefficient = kq_dev != nullptr;
+  }
+
   // The solve with a coefficient: CG on alpha M + tau S[kappa] from the initial
   // guess x, preconditioned by the constant-coefficient direct solve
   // (setup_system_solve first); SolverCG with ReductionControl(max_it,

@@ -321,9 +321,9 @@ int gdm_op_set_field_scale(gdm_op *op, const double *s);
  * gdm_apply_planes2 while a coefficient is set.  GDM_ERR_ARG: n_terms outside
  * [0, GDM_COEF_MAX_TERMS], a non-finite sample, and for n_terms = 1 a factor
  * that vanishes or changes sign.  For sums the caller guarantees kappa > 0.
- * Separable sums only: a general coefficient is sampled and fitted by a short
- * separable sum on the caller's side.  The density (a weighted mass) is set
- * by gdm_op_set_density below.
+ * Separable sums only here: a general coefficient, sampled on the tensor
+ * Gauss grid, is set by gdm_op_set_coefficient_grid below.  The density (a
+ * weighted mass) is set by gdm_op_set_density below.
  * ---------------------------------------------------------------------- */
 #define GDM_COEF_MAX_TERMS 4
 typedef struct {
@@ -335,6 +335,59 @@ int gdm_coef_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk
 int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms);
 int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, double *x, double rel_tol,
                    double abs_tol, int max_it, int *its_host, double *res_host);
+
+/* ------------------------------------------------------------------------
+ * General coefficient of the wave / heat / Poisson operator: kappa > 0 given
+ * pointwise on the tensor Gauss grid, the same K[kappa] and data term as above
+ * with kappa evaluated at every quadrature point (csrc/gdm_coefgrid.hip: one
+ * volume launch per apply and, with nitsche > 0, two small launches per box
+ * face; gather form, bitwise repeatable, nothing allocated per apply, a first
+ * apply can be captured in a hipGraph).
+ *
+ *   gdm_op_set_coefficient_grid
+ *       kq   DEVICE array in gdm_add_load's fq layout, kq[(qz Q_y + qy) Q_x +
+ *            qx], Q_d = n_sub_d (p+1), x fastest; the abscissae are entries
+ *            1..Q_d of gdm_field_points.
+ *       kbc  DEVICE array of kappa at the n_bc_points boundary points in device
+ *            block(0) order (gdm_bc_points; the order of g_bc of
+ *            gdm_add_dirichlet_data).  Required when the operator was created
+ *            with nitsche > 0, ignored (may be NULL) otherwise.
+ *       Both arrays are BORROWED, not copied: they must outlive the coefficient,
+ *       and the caller may overwrite the values in place between applies (a
+ *       time- or solution-dependent kappa); the next gdm_apply sees them.  The
+ *       call allocates all scratch, waits for the operator's stream and runs one
+ *       device reduction over kq (and kbc): GDM_ERR_ARG for a sample that is not
+ *       finite or not positive (the coefficient then stays as it was), and the
+ *       Gauss-weighted domain mean of kappa is stored for gdm_coef_solve's
+ *       preconditioner.  Calling it again with the same pointers refreshes that
+ *       mean.  kq == NULL removes the coefficient and restores the constant
+ *       operator bit for bit.  A grid coefficient replaces a separable one and
+ *       the other way round.
+ *   gdm_coef_grid_tile
+ *       pure host: the kernel's node tile and z chunk in kernel axes.  A 3D mesh
+ *       maps (x, y, z) to the kernel axes (x, y, z); a 2D mesh maps (x, y) to
+ *       (x, y) with a trivial z axis; a 1D mesh maps x to the kernel's z axis
+ *       with trivial x and y axes.
+ *   gdm_coef_grid_tables_1d
+ *       pure host: for each of the n_sub (p+1) Gauss points along `axis` the
+ *       p+1 basis values val[q (p+1) + i], the p+1 physical derivatives
+ *       der[q (p+1) + i] (divided by h) and first[q], the first node of the
+ *       cell's DoF box -- the tables the kernel uses.
+ * While a grid coefficient is set everything stated above for a separable
+ * coefficient holds: gdm_apply computes K[kappa] src (bc_values must be NULL),
+ * gdm_time_op(which = 0) times it, gdm_add_dirichlet_data uses kbc . g without
+ * modifying g_bc, gdm_coef_solve solves (alpha M - tau K[kappa]) -- (alpha
+ * M[rho] - tau K[kappa]) with a separable density set -- preconditioned at the
+ * mean of kappa, gdm_system_solve returns GDM_ERR_STATE, gdm_add_load* and the
+ * mass entry points are unchanged.  GDM_ERR_UNSUPPORTED: another operator
+ * kind, n_ranks > 1, a periodic mesh, the inner operator of a cut handle, and
+ * gdm_apply_planes / gdm_apply_planes2 while the coefficient is set.  For a
+ * kappa that is a separable sum gdm_op_set_coefficient is the faster path.
+ * ---------------------------------------------------------------------- */
+int gdm_op_set_coefficient_grid(gdm_op *op, const double *kq, const double *kbc);
+int gdm_coef_grid_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
+int gdm_coef_grid_tables_1d(const gdm_mesh_desc *mesh, int axis, double *val_host, double *der_host,
+                            int32_t *first_host);
 
 /* ------------------------------------------------------------------------
  * Separable density of the wave / heat operator: rho(x) = sum over the terms t
