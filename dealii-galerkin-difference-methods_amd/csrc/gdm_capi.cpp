@@ -18,6 +18,7 @@
 #include "../../include/gdm_hip.h"
 #include "gdm_coeffs.h"
 #include "gdm_coefgrid.h"
+#include "gdm_massgrid.h"
 #include "gdm_kernels.h"
 #include "gdm_load.h"
 #include "gdm_elasticity.h"
@@ -245,6 +246,18 @@ struct gdm_op {
     const LineTables *axis_tab[3] = {nullptr, nullptr, nullptr};
     double *w_isqrt = nullptr;  // [n_owned]: (diag M[rho] / diag M)^-1/2 (n_terms > 1)
     double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, K p
+    // per term and kernel axis diag(M_d[r_td]) (gdm_density_diag)
+    std::vector<std::vector<double>> band_diag;
+    // general density on the Gauss grid (gdm_op_set_density_grid): the launch
+    // plan of gdm_massgrid.hip; rq is the caller's array.  n_terms is 0, the
+    // solve is the CG with w_isqrt
+    bool grid = false;
+    gdmk::MgArgs grid_args{};  // src / dst / add / c filled per apply
+    double *mdiag = nullptr;   // [n_owned] diag(M): W of a grid density is formed from the current samples
+    const gdmk::CgAxis *grid_axes_dev = nullptr;  // the reduction's copy of grid_args.ax
+    double *grid_partial = nullptr;               // [2][1024] partial sums and bad counts of the reduction
+    double volume = 1.0;
+    int zc_auto = 0;  // mg_pick_zc of the mesh (gdm_op_set_density_grid_z_chunk restores it)
     std::vector<void *> allocations;
   } dens;
   bool cut_inner = false;  // the inner operator of a cut handle
@@ -2219,20 +2232,18 @@ void coef_grid_tables(int p, unsigned ncell, double h, CoefGridTables &T) {
   }
 }
 
-// Build the launch plan, tables and scratch of a grid coefficient into `nc`,
-// and run the reduction over kq (and kbc): false = a sample is not finite or
-// not positive.
-bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Coef &nc) {
+// The kernel axes of the tensor Gauss grid (gdm_coefgrid.hip, gdm_massgrid.hip)
+// into ax[3], every uploaded table recorded in `allocations`; a tile's footprint
+// is checked against the kernel's compile-time bounds (tile, Gauss points and
+// node span of kernel axes x and y).  Returns the volume of the box.
+double build_grid_axes(gdm_op *op, const int tile[2], const int nq_max[2], const int span_max[2], const char *what,
+                       std::vector<void *> &allocations, gdmk::CgAxis ax[3]) {
   const int p = op->p, n1 = p + 1;
   auto up = [&](const auto &h) {
     auto *d = dev_upload(h);
-    nc.allocations.push_back((void *)d);
+    allocations.push_back((void *)d);
     return d;
   };
-  nc.grid = true;
-  gdmk::CgArgs &a = nc.grid_args;
-  a = gdmk::CgArgs{};
-  a.kq = kq;
   double volume = 1.0;
   for (int k = 0; k < 3; ++k) {
     const int d = op->kdir[k];
@@ -2259,16 +2270,14 @@ bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Co
         qhi[(size_t)i] = std::max(qhi[(size_t)i], q + 1);
       }
     // the kernel's compile-time bounds on a tile's footprint
-    const int tile = k == 0 ? gdmk::cg_tx(p) : gdmk::cg_ty(p);
-    for (int i0 = 0; i0 < N && k < 2; i0 += tile) {
-      const int il = std::min(N, i0 + tile) - 1;
+    for (int i0 = 0; i0 < N && k < 2; i0 += tile[k]) {
+      const int il = std::min(N, i0 + tile[k]) - 1;
       const int q0 = qlo[(size_t)i0], q1 = qhi[(size_t)il];
       const int span = std::min(T.first[(size_t)q1 - 1] + p, N - 1) - T.first[(size_t)q0] + 1;
-      if (q1 <= q0 || q1 - q0 > (k == 0 ? gdmk::cg_nqx(p) : gdmk::cg_nqy(p)) ||
-          span > (k == 0 ? gdmk::cg_sx(p) : gdmk::cg_sy(p)))
-        throw std::runtime_error("grid coefficient: a tile's footprint exceeds the kernel's bounds");
+      if (q1 <= q0 || q1 - q0 > nq_max[k] || span > span_max[k])
+        throw std::runtime_error(std::string(what) + ": a tile's footprint exceeds the kernel's bounds");
     }
-    gdmk::CgAxis &A = a.ax[k];
+    gdmk::CgAxis &A = ax[k];
     A.N = N;
     A.Q = Q;
     A.first = up(T.first);
@@ -2278,6 +2287,26 @@ bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Co
     A.qlo = up(qlo);
     A.qhi = up(qhi);
   }
+  return volume;
+}
+
+// Build the launch plan, tables and scratch of a grid coefficient into `nc`,
+// and run the reduction over kq (and kbc): false = a sample is not finite or
+// not positive.
+bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Coef &nc) {
+  const int p = op->p, n1 = p + 1;
+  auto up = [&](const auto &h) {
+    auto *d = dev_upload(h);
+    nc.allocations.push_back((void *)d);
+    return d;
+  };
+  nc.grid = true;
+  gdmk::CgArgs &a = nc.grid_args;
+  a = gdmk::CgArgs{};
+  a.kq = kq;
+  const int tile[2] = {gdmk::cg_tx(p), gdmk::cg_ty(p)}, nq_max[2] = {gdmk::cg_nqx(p), gdmk::cg_nqy(p)},
+            span_max[2] = {gdmk::cg_sx(p), gdmk::cg_sy(p)};
+  const double volume = build_grid_axes(op, tile, nq_max, span_max, "grid coefficient", nc.allocations, a.ax);
   hip_check(gdmk::cg_prepare(p), "grid coefficient: LDS limit");
 
   // the box faces (Nitsche part)
@@ -2364,6 +2393,15 @@ bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Co
 
 // dst = M[rho] src (+ c * add)
 void density_apply(gdm_op *op, const double *src, double *dst, const double *add = nullptr, double c = 0.0) {
+  if (op->dens.grid) {
+    gdmk::MgArgs g = op->dens.grid_args;
+    g.src = src;
+    g.dst = dst;
+    g.add = add;
+    g.c = c;
+    hip_check(gdmk::launch_mg(op->p, g, op->stream), "grid density apply launch");
+    return;
+  }
   gdmk::VarMassArgs a = op->dens.args;
   a.src = src;
   a.dst = dst;
@@ -2448,6 +2486,17 @@ void build_density(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::
     nd.mean += prod;
   }
 
+  // diag(M_d[r_td]) per term and kernel axis (gdm_density_diag)
+  nd.band_diag.assign((size_t)n_terms * 3, std::vector<double>());
+  for (int t = 0; t < n_terms; ++t)
+    for (int ax = 0; ax < 3; ++ax) {
+      std::vector<double> &v = nd.band_diag[(size_t)t * 3 + ax];
+      v.assign((size_t)op->K[ax], 1.0);
+      if (op->kdir[ax] < 0) continue;
+      const gdm::Band &B = tabs[term_tab[t][ax]].B;
+      for (int i = 0; i < op->K[ax]; ++i) v[(size_t)i] = B(i, i);
+    }
+
   const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
   if (n_terms == 1) {
     // M[rho]^-1 = (x)_d M_d[r_d]^-1: the two-sweep line tables of every factor;
@@ -2492,6 +2541,102 @@ void build_density(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::
   }
   for (double *&v : nd.cg) v = up(std::vector<double>(n, 0.0));
   nd.active = true;
+}
+
+// ---- general density on the Gauss grid (gdm_massgrid.hip) -------------------
+
+// W^-1/2 = (diag M[rho] / diag M)^-1/2 of a grid density from the samples as they are
+// now: the kernel's diagonal mode into a CG vector, then the ratio (two launches)
+void density_grid_scaling(gdm_op *op, gdm_op::Density &D) {
+  gdmk::MgArgs g = D.grid_args;
+  g.dst = D.cg[2];
+  hip_check(gdmk::launch_mg_diag(op->p, g, op->stream), "grid density diagonal launch");
+  hip_check(gdmk_mg_wisqrt(op->layout.n_owned, D.cg[2], D.mdiag, D.w_isqrt, op->stream), "grid density scaling");
+}
+
+// One reduction over the samples of a grid density: the Gauss-weighted mean into
+// *mean (1024 block partials, summed here in a fixed order); false = a sample is
+// not finite or not positive
+constexpr int kGridBlocks = 1024;
+bool density_grid_reduce(gdm_op *op, const gdm_op::Density &D, double *mean) {
+  const gdmk::MgArgs &a = D.grid_args;
+  const int64_t nq = (int64_t)a.ax[0].Q * a.ax[1].Q * a.ax[2].Q;
+  hip_check(gdmk_cg_reduce(a.rq, nq, D.grid_axes_dev, D.grid_partial, D.grid_partial + kGridBlocks, kGridBlocks,
+                           op->stream), "grid density reduction");
+  std::vector<double> host((size_t)2 * kGridBlocks);
+  hip_check(hipMemcpyAsync(host.data(), D.grid_partial, sizeof(double) * host.size(), hipMemcpyDeviceToHost,
+                           op->stream), "copy");
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  double sum = 0.0, bad = 0.0;
+  for (int b = 0; b < kGridBlocks; ++b) {
+    sum += host[(size_t)b];
+    bad += host[(size_t)kGridBlocks + b];
+  }
+  *mean = sum / D.volume;
+  return bad == 0.0;
+}
+
+// Build the launch plan, tables and scratch of a grid density into `nd`, run the
+// reduction over rq (false = a sample is not finite or not positive) and form
+// W^-1/2 = (diag M[rho] / diag M)^-1/2 of the preconditioner on the device.
+bool build_density_grid(gdm_op *op, const double *rq, gdm_op::Density &nd) {
+  const int p = op->p;
+  auto up = [&](const auto &h) {
+    auto *d = dev_upload(h);
+    nd.allocations.push_back((void *)d);
+    return d;
+  };
+  nd.grid = true;
+  nd.n_terms = 0;
+  gdmk::MgArgs &a = nd.grid_args;
+  a = gdmk::MgArgs{};
+  a.rq = rq;
+  const int tile[2] = {gdmk::mg_tx(p), gdmk::mg_ty(p)}, nq_max[2] = {gdmk::mg_nqx(p), gdmk::mg_nqy(p)},
+            span_max[2] = {gdmk::mg_sx(p), gdmk::mg_sy(p)};
+  const double volume = build_grid_axes(op, tile, nq_max, span_max, "grid density", nd.allocations, a.ax);
+  if ((int64_t)a.ax[0].N * a.ax[1].N * a.ax[2].N != op->layout.n_owned)
+    throw std::runtime_error("grid density: the kernel axes do not cover the owned DoFs");
+  int n_cu = 0;
+  hip_check(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, op->device), "hipDeviceGetAttribute");
+  nd.zc_auto = a.zc = gdmk::mg_pick_zc(p, a.ax[0].N, a.ax[1].N, a.ax[2].N, n_cu);
+  hip_check(gdmk::mg_prepare(p), "grid density: LDS limit");
+  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
+  for (double *&v : nd.cg) v = up(std::vector<double>(n, 0.0));
+  nd.w_isqrt = up(std::vector<double>(n, 1.0));
+  nd.mdiag = up(mass_diagonal_owned(op));
+
+  std::vector<gdmk::CgAxis> axes(a.ax, a.ax + 3);
+  nd.grid_axes_dev = up(axes);
+  nd.grid_partial = up(std::vector<double>((size_t)2 * kGridBlocks, 0.0));
+  nd.volume = volume;
+  double mean = 0.0;
+  if (!density_grid_reduce(op, nd, &mean)) return false;
+  nd.mean = mean;
+  density_grid_scaling(op, nd);
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  nd.active = true;
+  return true;
+}
+
+// the refusals shared by gdm_op_set_density and gdm_op_set_density_grid; 0 = ok
+int check_density_op(gdm_op *op, const char *what) {
+  const std::string w(what);
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, w + ": wave operators only");
+  if (op->cut_inner)
+    return fail(GDM_ERR_UNSUPPORTED, w + ": the cut-cell rows of a cut handle are assembled for the unit density");
+  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, w + ": single rank only");
+  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, w + ": not with periodic constraints");
+  return GDM_OK;
+}
+
+// install `nd` as the operator's density (applies in flight read the old tables)
+void install_density(gdm_op *op, gdm_op::Density &nd) {
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
+  op->dens = std::move(nd);
+  // the pointers into the moved-from object
+  for (int ax = 0; ax < 3; ++ax) op->dens.axis_tab[ax] = op->dens.axis_tab[ax] ? &op->dens.tab[ax] : nullptr;
 }
 }  // namespace
 
@@ -2830,13 +2975,7 @@ int gdm_density_cholesky_1d(const gdm_mesh_desc *mesh, int axis, const double *f
 }
 
 int gdm_op_set_density(gdm_op *op, int n_terms, const gdm_coef_term *terms) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: wave operators only");
-  if (op->cut_inner)
-    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: the cut-cell rows of a cut handle are assembled for the "
-                                     "unit density");
-  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: single rank only");
-  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_density: not with periodic constraints");
+  if (int rc = check_density_op(op, "gdm_op_set_density")) return rc;
   if (n_terms < 0 || n_terms > GDM_COEF_MAX_TERMS)
     return fail(GDM_ERR_ARG, "gdm_op_set_density: n_terms must be in [0, GDM_COEF_MAX_TERMS]");
   if (n_terms > 0 && !terms) return fail(GDM_ERR_ARG, "gdm_op_set_density: terms is NULL");
@@ -2866,12 +3005,93 @@ int gdm_op_set_density(gdm_op *op, int n_terms, const gdm_coef_term *terms) {
       throw;
     }
   }
-  // applies in flight read the old tables
+  install_density(op, nd);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_density_grid_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
+  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (tile_x) *tile_x = gdmk::mg_tx(fe_degree);
+  if (tile_y) *tile_y = gdmk::mg_ty(fe_degree);
+  if (z_chunk) *z_chunk = gdmk::mg_zc(fe_degree);
+  return GDM_OK;
+}
+
+int gdm_op_set_density_grid(gdm_op *op, const double *rq) {
+  if (int rc = check_density_op(op, "gdm_op_set_density_grid")) return rc;
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  // the reduction and the diagonal run on the operator's stream behind whatever wrote rq there
   hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
-  op->dens = std::move(nd);
-  // the pointers into the moved-from object
-  for (int ax = 0; ax < 3; ++ax) op->dens.axis_tab[ax] = op->dens.axis_tab[ax] ? &op->dens.tab[ax] : nullptr;
+  const char *bad_sample = "gdm_op_set_density_grid: a sample of rho is not finite or not positive";
+  if (rq && op->dens.active && op->dens.grid && op->dens.grid_args.rq == rq) {
+    // the same pointer: the tables and the scratch stand, the mean and W follow the samples
+    double mean = 0.0;
+    if (!density_grid_reduce(op, op->dens, &mean)) return fail(GDM_ERR_ARG, bad_sample);
+    op->dens.mean = mean;
+    density_grid_scaling(op, op->dens);
+    hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+    return GDM_OK;
+  }
+  gdm_op::Density nd;
+  if (rq) {
+    bool ok = true;
+    try {
+      ok = build_density_grid(op, rq, nd);
+    } catch (...) {
+      for (void *ptr : nd.allocations) (void)hipFree(ptr);
+      throw;
+    }
+    if (!ok) {
+      for (void *ptr : nd.allocations) (void)hipFree(ptr);
+      return fail(GDM_ERR_ARG, bad_sample);
+    }
+  }
+  install_density(op, nd);
+  return GDM_OK;
+  GDM_GUARD_END
+}
+
+int gdm_op_set_density_grid_z_chunk(gdm_op *op, int z_chunk) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (!op->dens.active || !op->dens.grid)
+    return fail(GDM_ERR_STATE, "gdm_op_set_density_grid_z_chunk: no grid density is set (gdm_op_set_density_grid)");
+  if (z_chunk == 0 || z_chunk < -1 || z_chunk > gdmk::mg_zc(op->p))
+    return fail(GDM_ERR_ARG, "gdm_op_set_density_grid_z_chunk: z_chunk must be -1 or in [1, the chunk of "
+                             "gdm_density_grid_tile]");
+  op->dens.grid_args.zc = z_chunk < 0 ? op->dens.zc_auto : z_chunk;
+  return GDM_OK;
+}
+
+int gdm_density_diag(gdm_op *op, double *dst_owned) {
+  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
+  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_diag: no density is set (gdm_op_set_density[_grid])");
+  if (!dst_owned) return fail(GDM_ERR_ARG, "NULL vector");
+  GDM_GUARD_BEGIN
+  hip_check(hipSetDevice(op->device), "hipSetDevice");
+  const gdm_op::Density &D = op->dens;
+  if (D.grid) {
+    gdmk::MgArgs g = D.grid_args;
+    g.dst = dst_owned;
+    hip_check(gdmk::launch_mg_diag(op->p, g, op->stream), "grid density diagonal launch");
+    return GDM_OK;
+  }
+  // separable: sum_t prod_d diag(M_d[r_td]), 1D tables from the set call
+  const int Nx = op->K[0], Ny = op->K[1], Nz = op->K[2];
+  std::vector<double> h((size_t)Nx * Ny * Nz);
+  for (int z = 0; z < Nz; ++z)
+    for (int y = 0; y < Ny; ++y)
+      for (int x = 0; x < Nx; ++x) {
+        double s = 0.0;
+        for (int t = 0; t < D.n_terms; ++t)
+          s += D.band_diag[(size_t)t * 3][(size_t)x] * D.band_diag[(size_t)t * 3 + 1][(size_t)y] *
+               D.band_diag[(size_t)t * 3 + 2][(size_t)z];
+        h[((size_t)z * Ny + y) * Nx + x] = s;
+      }
+  hip_check(hipMemcpyAsync(dst_owned, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, op->stream), "copy");
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
   return GDM_OK;
   GDM_GUARD_END
 }
@@ -2904,7 +3124,8 @@ int gdm_density_solve(gdm_op *op, const double *rhs, double *x, double rel_tol, 
   if (!op) return fail(GDM_ERR_ARG, "op is NULL");
   if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_solve: no density is set (gdm_op_set_density)");
   if (!rhs || !x) return fail(GDM_ERR_ARG, "NULL vector");
-  if (op->dens.n_terms > 1 && rhs == x) return fail(GDM_ERR_ARG, "gdm_density_solve: a sum of terms needs rhs != x");
+  if (op->dens.n_terms != 1 && rhs == x)
+    return fail(GDM_ERR_ARG, "gdm_density_solve: a sum of terms or a grid density needs rhs != x");
   if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
@@ -2918,6 +3139,8 @@ int gdm_density_solve(gdm_op *op, const double *rhs, double *x, double rel_tol, 
     return GDM_OK;
   }
   double *r = D.cg[0], *p = D.cg[1], *Ap = D.cg[2], *z = D.cg[3];
+  // the caller may have overwritten a borrowed grid in place: W follows the samples of this solve
+  if (D.grid) density_grid_scaling(op, D);
   auto dot = [&](const double *u, const double *v) {
     double s = 0.0;
     if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");

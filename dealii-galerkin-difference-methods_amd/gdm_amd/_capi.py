@@ -176,6 +176,11 @@ def load():
         "gdm_density_apply": [P, P, P],
         "gdm_density_apply_add": [P, P, d, P, P],
         "gdm_density_solve": [P, P, P, d, d, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(d)],
+        "gdm_op_set_density_grid": [P, P],
+        "gdm_density_grid_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                  ctypes.POINTER(ctypes.c_int)],
+        "gdm_density_diag": [P, P],
+        "gdm_op_set_density_grid_z_chunk": [P, i32],
         "gdm_mass_apply": [P, P, P],
         "gdm_mass_solve": [P, P, P],
         "gdm_mass_solve_rk": [P, P, d, P, P, d, P, P],
@@ -416,6 +421,14 @@ def density_tile(fe_degree, dim):
     """(tile_x, tile_y, z_chunk) of the density kernel, kernel axes (gdm_density_tile)"""
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_density_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_density_tile")
+    return tuple(v.value for v in t)
+
+
+def density_grid_tile(fe_degree, dim):
+    """(tile_x, tile_y, z_chunk) of the grid density kernel, kernel axes (gdm_density_grid_tile)"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_density_grid_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]),
+          "gdm_density_grid_tile")
     return tuple(v.value for v in t)
 
 

@@ -335,6 +335,15 @@ class GdmOperator:
         entries 1 .. Q_d of field_points(d), Q_d = n_sub_d (p + 1)."""
         return [_capi.field_points(self.mesh, d)[1:-1] for d in range(self.dim)]
 
+    def gauss_grid_points(self):
+        """the tensor Gauss grid as (n, 3) points in add_load's order (qz, qy, qx)"""
+        xq = self.quadrature_points() + [np.zeros(1)] * (3 - self.dim)
+        x = np.zeros((xq[2].size, xq[1].size, xq[0].size, 3))
+        x[..., 0] = xq[0][None, None, :]
+        x[..., 1] = xq[1][None, :, None]
+        x[..., 2] = xq[2][:, None, None]
+        return x.reshape(-1, 3)
+
     def add_load_fn(self, fn_kind, params, t, dst_owned, derivative=0, scale=1.0):
         """dst += scale (v, f) over QGauss(p+1), f a built-in function at time
         t or (derivative=1) its d/dt (gdm_add_load_fn; wave/stiffness.h:196-200)"""
@@ -458,12 +467,7 @@ class GdmOperator:
         dev = "cuda:%d" % self.device
         if callable(kq):
             kappa = kq
-            xq = self.quadrature_points() + [np.zeros(1)] * (3 - self.dim)
-            x = np.zeros((xq[2].size, xq[1].size, xq[0].size, 3))
-            x[..., 0] = xq[0][None, None, :]
-            x[..., 1] = xq[1][None, :, None]
-            x[..., 2] = xq[2][:, None, None]
-            kq = torch.from_numpy(np.ascontiguousarray(kappa(x.reshape(-1, 3)), dtype=np.float64)).to(dev)
+            kq = torch.from_numpy(np.ascontiguousarray(kappa(self.gauss_grid_points()), dtype=np.float64)).to(dev)
             if self.n_bc_points > 0:  # ignored by an operator without Nitsche terms
                 kbc = torch.from_numpy(np.ascontiguousarray(kappa(self.bc_points()), dtype=np.float64)).to(dev)
         nq = 1
@@ -516,10 +520,58 @@ class GdmOperator:
         arr, _keep = self._coef_terms(terms, "set_density")
         check(self.lib.gdm_op_set_density(self.h, len(terms), arr if terms else None), "gdm_op_set_density")
         self.n_density_terms = len(terms)
+        self._density_grid = None  # a separable density replaces a grid one
+
+    def set_density_grid(self, rq):
+        """A general rho > 0 sampled on the tensor Gauss grid
+        (gdm_op_set_density_grid; wave operators).  rq is a device tensor in
+        add_load's layout rq[(qz Q_y + qy) Q_x + qx] (quadrature_points()); the
+        engine borrows it, the operator keeps the reference, and values
+        overwritten in place are seen by the next density_apply and
+        density_solve (call this again with the same tensor to refresh the
+        mean that coef_solve's preconditioner uses).  rq may also be a callable
+        rho(x), x of shape (n, 3): it is evaluated on the host at the Gauss
+        grid and uploaded.  None removes the density."""
+        if rq is None:
+            check(self.lib.gdm_op_set_density_grid(self.h, None), "gdm_op_set_density_grid")
+            self._density_grid = None
+            self.n_density_terms = 0
+            return
+        if callable(rq):
+            rho = np.ascontiguousarray(rq(self.gauss_grid_points()), dtype=np.float64)
+            rq = self._torch.from_numpy(rho).to("cuda:%d" % self.device)
+        nq = 1
+        for d in range(self.dim):
+            nq *= self.mesh.n_subdivisions[d] * (self.p + 1)
+        if rq.numel() != nq:
+            raise GdmError("set_density_grid: rq has %d entries, the quadrature grid %d" % (rq.numel(), nq))
+        check(self.lib.gdm_op_set_density_grid(self.h, _ptr(rq)), "gdm_op_set_density_grid")
+        self._density_grid = rq  # keeps the borrowed memory alive
+        self.n_density_terms = 0
 
     @property
     def has_density(self):
-        return getattr(self, "n_density_terms", 0) > 0
+        return getattr(self, "n_density_terms", 0) > 0 or getattr(self, "_density_grid", None) is not None
+
+    def density_grid_tile(self):
+        """(tile_x, tile_y, z_chunk) of the grid density kernel, kernel axes"""
+        return _capi.density_grid_tile(self.p, self.dim)
+
+    def set_density_grid_z_chunk(self, z_chunk=-1):
+        """node planes per workgroup of the grid density kernel, in [1,
+        density_grid_tile()[2]]; -1 restores the automatic choice.  Steers the
+        launch only: the bits do not depend on it
+        (gdm_op_set_density_grid_z_chunk)"""
+        check(self.lib.gdm_op_set_density_grid_z_chunk(self.h, int(z_chunk)), "gdm_op_set_density_grid_z_chunk")
+
+    def density_diag(self, dst_owned=None):
+        """dst = diag(M[rho]) of the density that is set, grid or separable
+        (gdm_density_diag)"""
+        if dst_owned is None:
+            dst_owned = self.new_vector(False)
+        self._check_sizes(None, dst_owned)
+        check(self.lib.gdm_density_diag(self.h, _ptr(dst_owned)), "gdm_density_diag")
+        return dst_owned
 
     def density_tile(self):
         """(tile_x, tile_y, z_chunk) of the density kernel, kernel axes"""

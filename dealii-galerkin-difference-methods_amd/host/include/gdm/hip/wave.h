@@ -224,6 +224,21 @@ class StiffnessMatrixOperator {
     has_density = !terms.empty();
   }
 
+  // A general density rho > 0 given by its samples on the tensor Gauss grid
+  // (gdm_op_set_density_grid, after reinit; single rank): rq_dev is a DEVICE
+  // array in the layout of set_coefficient_grid's kq, borrowed by the engine:
+  // it must outlive the density, and values overwritten in place are seen by
+  // the next density_apply and density_solve (call this again to refresh the
+  // mean that solve()'s preconditioner uses).
+  // nullptr: the unit density again.
+  void set_density_grid(const double *rq_dev) {
+    check(gdm_op_set_density_grid(op, rq_dev), "gdm_op_set_density_grid");
+    has_density = rq_dev != nullptr;
+  }
+
+  // dst = diag(M[rho]) of the density that is set, grid or separable
+  void density_diag(double *dst_owned) const { check(gdm_density_diag(op, dst_owned), "gdm_density_diag"); }
+
   // dst = M[rho] src (distinct device vectors)
   void density_apply(double *dst_owned, const double *src_owned) const {
     check(gdm_density_apply(op, src_owned, dst_owned), "gdm_density_apply");

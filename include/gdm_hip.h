@@ -452,6 +452,65 @@ int gdm_density_apply_add(gdm_op *op, const double *src, double c, const double 
 int gdm_density_solve(gdm_op *op, const double *rhs, double *x, double rel_tol, double abs_tol, int max_it,
                       int *its_host, double *res_host);
 
+/* ------------------------------------------------------------------------
+ * General density on the Gauss grid: rho given by its samples on the tensor
+ * Gauss grid of the mesh, for a density that is no short separable sum (a
+ * model read from a file, a curved inclusion, a random field, rho(u)
+ * re-evaluated every step).  M[rho] u = (B_z (x) B_y (x) B_x)^T diag(w rho)
+ * (B_z (x) B_y (x) B_x) u with the value tables of gdm_coef_grid_tables_1d:
+ * one launch of csrc/gdm_massgrid.hip, gather form, bitwise repeatable,
+ * nothing allocated per apply.
+ *
+ *   gdm_op_set_density_grid
+ *       rq is a DEVICE array in gdm_add_load's layout rq[(qz Q_y + qy) Q_x + qx]
+ *       (the grid of kq), BORROWED, not copied: it must outlive the density, and
+ *       the caller may overwrite it in place; the next gdm_density_apply sees
+ *       the new values.  The call waits for the operator's stream, allocates all
+ *       scratch, runs one device reduction (a sample that is not finite or not
+ *       positive: GDM_ERR_ARG, the operator stays as it was), forms the
+ *       Gauss-weighted mean of rho (fixed-order partials summed on the host) and
+ *       W^-1/2 with W = diag(M[rho]) / diag(M) on the device.  Calling it again
+ *       with the same pointer refreshes the mean and W and keeps the tables and
+ *       the scratch (one reduction and the diagonal launch, nothing allocated).
+ *       After an in-place overwrite WITHOUT this call the apply is current, and
+ *       gdm_density_solve forms W again from the samples it finds (one launch of
+ *       the kernel's diagonal mode per solve), but the mean in gdm_coef_solve's
+ *       preconditioner is the old rho's: still SPD, so that CG converges, only
+ *       more slowly.
+ *       rq = NULL removes the density.  A grid density replaces a separable one
+ *       and the other way round.
+ *   gdm_density_grid_tile
+ *       pure host: the (x, y) tile and the largest z chunk of the kernel,
+ *       kernel axes (2D: z trivial; 1D: the mesh's x is the kernel's z).  A
+ *       mesh with fewer than two workgroups per CU runs with a half or a
+ *       quarter of the z chunk; the bits do not depend on it.
+ *   gdm_op_set_density_grid_z_chunk
+ *       steers the launch like gdm_op_set_mass_seg_waves and changes no bit of a
+ *       result: z_chunk in [1, the chunk of gdm_density_grid_tile] node planes
+ *       per workgroup, -1 restores the automatic choice; GDM_ERR_ARG otherwise,
+ *       GDM_ERR_STATE without a grid density.  A new set call (not a refresh)
+ *       chooses automatically again.
+ *   gdm_density_diag
+ *       dst_owned = diag(M[rho]) of the density that is set: on the grid
+ *       sum_q w_q rho_q prod_d B_d[q_d, i_d]^2 by the kernel's diagonal mode,
+ *       for a separable density sum_t prod_d diag(M_d[r_td]).  GDM_ERR_STATE
+ *       without a density.
+ * With a grid density set gdm_density_apply[_add] launch the grid kernel,
+ * gdm_time_op(which = 3) times it, gdm_density_solve is always the CG described
+ * above (rhs != x; preconditioner W^-1/2 M^-1 W^-1/2; the same GDM_ERR_STATE
+ * returns) and gdm_coef_solve solves (alpha M[rho] - tau K[kappa]) x = rhs for
+ * kappa absent, separable or on the grid, preconditioned at (mean(rho),
+ * mean(kappa)).  Nothing else changes; without a grid density every launch is
+ * the one it was.  GDM_ERR_UNSUPPORTED as for gdm_op_set_density: another
+ * operator kind, n_ranks > 1, a periodic mesh, the inner operator of a cut
+ * handle.  For a rho that is a separable sum gdm_op_set_density is the faster
+ * path.
+ * ---------------------------------------------------------------------- */
+int gdm_op_set_density_grid(gdm_op *op, const double *rq);
+int gdm_density_grid_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
+int gdm_op_set_density_grid_z_chunk(gdm_op *op, int z_chunk);
+int gdm_density_diag(gdm_op *op, double *dst_owned);
+
 /* dst_owned = M src_local */
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned);
 /* x_owned = M^-1 rhs_owned (exact Kronecker inverse; single rank; not with
