@@ -3,312 +3,39 @@
 // Owns the device-side operator state: 1D band tables in kernel order, the
 // banded Cholesky factors of the 1D mass matrices, the inflow-face projection
 // tables and the slab layout.  All launches go to the operator's stream.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+// The variable coefficient and density, the elasticity operator and the cut
+// handles have units of their own (gdm_capi_coef.cpp, gdm_capi_elasticity.cpp,
+// gdm_capi_cut.cpp); gdm_capi_internal.h is what they share.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
-#include "../../include/gdm_hip.h"
+#include "gdm_capi_internal.h"
 #include "gdm_coeffs.h"
-#include "gdm_coefgrid.h"
-#include "gdm_massgrid.h"
-#include "gdm_kernels.h"
 #include "gdm_load.h"
-#include "gdm_elasticity.h"
-#include "gdm_fastdiag.h"
-#include "gdm_periodic.h"
 #include "gdm_post.h"
-#include "gdm_rk.h"
-#include "gdm_setup.h"
-#include "gdm_vardiff.h"
-#include "gdm_varmass.h"
-#include "gdm_varstencil.h"
+
+using namespace gdm_detail;
 
 namespace {
 
 thread_local std::string g_last_error;
 
-int fail(int code, const std::string &msg) {
+}  // namespace
+
+int gdm_detail::fail(int code, const std::string &msg) {
   g_last_error = msg;
   return code;
 }
 
-struct HipError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-void hip_check(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-template <typename T>
-T *dev_upload(const std::vector<T> &h) {
-  T *d = nullptr;
-  const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-  hip_check(hipMalloc(&d, bytes), "hipMalloc");
-  if (!h.empty()) hip_check(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
-  return d;
-}
-
-// one tangential direction of a boundary face
-struct FaceDir {
-  int dim_index = -1;     // reference direction, -1 = trivial
-  int n_nodes = 1;        // nodes along this direction
-  int Q = 1;              // quadrature points along this direction (local cells x (p+1))
-  int cell_begin = 0;     // first local cell
-  int node_begin = 0, node_end = 1;  // output node range (owned)
-  int64_t stride = 0;     // global index stride
-  int wmax = 1;
-  int qmax = 1;           // largest q-range of FACE_CHUNK consecutive owned nodes
-  int *qs = nullptr, *qc = nullptr;
-  double *w = nullptr;    // [n_nodes][wmax]
-  double *wT = nullptr;   // [wmax][n_nodes]
-  double *phi = nullptr;  // [p][p+1][p+1] cell tables (cell form of the face step 1)
-  int *crange = nullptr;  // [n_nodes][2] first / last local cell of each node
-  int ncell_total = 0;
-};
-
-struct Face {
-  int d = 0, side = 0;
-  double scale = 0.0;     // |a.n| for inflow faces, 0 otherwise
-  int64_t offset = 0;     // offset into the device bc array
-  int64_t n_points = 0;
-  FaceDir t0, t1;
-  int64_t base = 0;       // owned index of node (i0 = 0, i1 = t1.node_begin)
-  double *T = nullptr;    // step-1 result of this face (faces run concurrently)
-};
-
-}  // namespace
-
 // shared with the sparse-matrix entry points (gdm_csr.hip)
 int gdm_internal_set_error(int code, const char *msg) { return fail(code, msg); }
-
-// line-solve tables of one banded SPD matrix (build_line_tables)
-struct LineTables {
-  double *lrow = nullptr, *invd = nullptr;               // v2 row form
-  double *l3 = nullptr, *u3 = nullptr, *d3 = nullptr;    // v3 split rows
-  std::vector<double> cst;                               // v3 interior fixed-point row
-  int row_lo = 0, row_hi = 0;
-};
-
-// Distributed exact mass inverse along the partitioned direction (truncated
-// SPIKE, gdm_mass_solve_slab / gdm_mass_solve_interface): the slab's own
-// diagonal block A_r of M_q, its spikes V = A_r^-1 B_r (coupling to the next
-// slab's first p planes) and W = A_r^-1 C_r (previous slab's last p planes),
-// and the two p x 2p rows of the interface-system inverses.
-struct SpikeTables {
-  bool built = false;
-  double eps = 0.0;        // largest dropped far-spike entry over all slabs
-  int rounds = 0;          // refinement exchanges (-1: partition refused)
-  int next_round = -1;     // progress of the current solve: -1 no slab solve
-                           // pending, k: rounds [0, k) done
-  double *G0 = nullptr;    // device [2p][plane]: saved slab-solve edge planes (rounds > 0)
-  int n_planes = 0;        // owned planes of this rank
-  int has_lo = 0, has_hi = 0;
-  LineTables slab;         // A_r
-  double *VW = nullptr;    // device [n_planes][2p]: V row k | W row k
-  double *S = nullptr;     // device [2][p][2p]: lower-interface rows (x_{r-1}^bot), upper (x_{r+1}^top)
-  int k_begin = 0, k_end = 0;  // planes the correction touches
-};
-
-// Exact mass inverse with periodicity constraints (gdm_mass_solve_periodic):
-// per periodic direction the line tables of A~ = blockdiag(A, 1) (kernel axis
-// of the direction) and the rank-2 Woodbury correction (gdm_periodic.hip); w =
-// the gather scratch [2][most lines of a periodic direction].  All of it is
-// built by gdm_op_create, so the first solve may run inside a stream capture.
-struct PeriodicMass {
-  LineTables tab[3];           // by kernel axis
-  const LineTables *axis_tab[3] = {nullptr, nullptr, nullptr};
-  gdmk::PeriodicDir dir[3]{};  // by reference direction
-  double *w = nullptr;
-};
-
-struct gdm_op {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  bool concurrent = true;  // compute_rhs: face step 1 in the stencil's tail (apply_with_faces)
-  gdm_mesh_desc mesh{};
-  int kind = 0, p = 1, dim = 1;
-  int N[3] = {1, 1, 1};        // vertices per reference direction
-  int K[3] = {1, 1, 1};        // kernel-space extents (X, Y, Z)
-  int kdir[3] = {-1, -1, -1};  // kernel axis -> reference direction (-1 trivial)
-  int part_axis = 2;           // kernel axis of the slab partition (1 = Y, 2 = Z)
-  gdm_layout layout{};
-  double a[3] = {0, 0, 0};
-  double nitsche = 0.0;
-  // device tables
-  // stencil tables (kernel axes) and the scalars of the compile-time bands
-  double *corrX = nullptr, *yT1 = nullptr, *yT3 = nullptr, *zt = nullptr;
-  int x_corr_left = 0, x_corr_right = 0, x_toep = 0, y_toep = 0, z_toep = 0;
-  double sx = 0, cy[19] = {0};
-  // v8 variants: E pre-scaled by h_z (sx, cy, corrX's B part, yT3), z table e = M_z / h_z
-  double *corrX8 = nullptr, *yT3_8 = nullptr, *zt8 = nullptr;
-  double *yT1d = nullptr, *yT3d = nullptr, *m_yT3d = nullptr;  // v8 y corrections
-  double sx8 = 0, cy8[19] = {0}, cxs8[19] = {0};
-  double dint = 0, m_dint = 0;  // interior z scales of D (operator, mass)
-  double zd8[19] = {0}, m_zd8[19] = {0};  // dint * dhat[2p - k] (operator, mass)
-  int xcd_map = 1;
-  // the same for the mass operator of an advection/wave op (gdm_mass_apply)
-  double *m_corrX = nullptr, *m_zt = nullptr;
-  double *lrow[3] = {nullptr, nullptr, nullptr}, *invd[3] = {nullptr, nullptr, nullptr};
-  // mass inverse v3 tables (gdm_mass.hip): [rows][p] lower / upper factor rows,
-  // inverse diagonal, the interior fixed-point row and its row range
-  double *l3[3] = {nullptr, nullptr, nullptr}, *u3[3] = {nullptr, nullptr, nullptr}, *d3[3] = {nullptr, nullptr, nullptr};
-  double *cst3[3] = {nullptr, nullptr, nullptr};
-  int row_lo3[3] = {0, 0, 0}, row_hi3[3] = {0, 0, 0};
-  std::vector<double> cst3_host[3];
-  double *bc_tab = nullptr;  // gdm_eval_boundary: per-face 1D factor tables
-  SpikeTables spike;         // distributed mass inverse (n_ranks > 1)
-  PeriodicMass pmass;        // exact mass inverse with periodicity constraints
-  // gdm_error_norms: shape values per category, per-workgroup partials, result
-  double *err_S = nullptr, *err_partial = nullptr;
-  static constexpr int n_err_partial = 1024;
-  int bc_tab_ld = 0;
-  double *bc_stage_tab = nullptr;  // gdm_apply_bc_fn: BcStage factor tables (2 x 6 faces)
-  double *bc_stage_vals = nullptr;  // gdm_apply_bc_fn: the stage boundary values (n_bc_points)
-  int bc_stage_ld = 0;
-  // periodicity constraints (system.h:427-463): scratch copy of the input for
-  // distribute; CG work vectors and the Jacobi inverse diagonal
-  double *pscratch = nullptr;
-  double *cg_r = nullptr, *cg_p = nullptr, *cg_Ap = nullptr, *cg_z = nullptr, *cg_invdiag = nullptr;
-  std::vector<Face> faces;
-  double *face_tmp = nullptr;
-  // the stencil's tail work (face step 1, gdmk_launch_stencil8): device claim
-  // counter, 0 between launches (each launch resets it with its last claim)
-  unsigned long long *tail_counter = nullptr;
-  double *mass_tmp = nullptr;  // ping-pong vector of the segmented mass passes (small meshes)
-  int64_t mass_tmp_size = 0;
-  int mass_seg_waves = -1;      // gdm_op_set_mass_seg_waves (-1: gdmk_mass3_seg_waves())
-  gdm_mass_path mass_path = {};  // what the last mass_solve_passes launched (gdm_op_mass_path)
-  int64_t face_tmp_size = 0;
-  double *dot_partial = nullptr, *dot_out = nullptr;
-  int n_dot_partial = 1024;
-  int zchunk = 64;
-  // host copies for bc ordering
-  std::vector<double> xq;
-  gdm::Slab slab{};
-  std::vector<void *> allocations;
-  // separable advection field (gdm_op_set_advection_field): the launch plan of
-  // the volume kernel and the per-face arguments, all device memory allocated
-  // when the field is set
-  struct Field {
-    bool active = false;
-    int n_terms = 0;
-    double scale[gdmk::VAR_MAX_TERMS];       // s_t (gdm_op_set_field_scale)
-    gdmk::VarArgs vol{};                     // src / dst / scale filled per apply
-    size_t lds = 0;
-    std::vector<gdmk::VarFaceArgs> faces;    // u / bc / dst / coef filled per apply
-    std::vector<int64_t> face_bc_offset;
-    // per face and face term: the term and sign * f_normal(end) (coef = that * s_t)
-    std::vector<std::vector<int>> face_term;
-    std::vector<std::vector<double>> face_end;
-    std::vector<void *> allocations;
-  } field;
-  // separable coefficient of the wave operator (gdm_op_set_coefficient): the
-  // launch plan of gdm_vardiff.hip, kappa at the boundary points with the
-  // scratch of kappa g, the domain mean of kappa and the CG vectors of
-  // gdm_coef_solve, all device memory allocated when the coefficient is set
-  struct Coef {
-    bool active = false;
-    int n_terms = 0;
-    gdmk::DiffArgs args{};  // src / dst filled per apply
-    size_t lds = 0;
-    double *kappa_bc = nullptr, *g_scaled = nullptr;  // [n_bc_points]
-    double mean = 1.0;
-    double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, M p
-    // general coefficient on the Gauss grid (gdm_op_set_coefficient_grid): the
-    // launch plan of gdm_coefgrid.hip; kq and kappa_bc are the caller's arrays
-    bool grid = false;
-    gdmk::CgArgs grid_args{};  // src / dst filled per apply
-    std::vector<gdmk::CgFace> grid_faces;
-    double *face_scratch = nullptr;  // [2][largest face's Gauss points]
-    std::vector<void *> allocations;
-  } coef;
-  // separable density of the wave operator (gdm_op_set_density): the launch
-  // plan of gdm_varmass.hip, the domain mean of rho, for one term the two-sweep
-  // line tables of every M_d[r_d] (by kernel axis), for sums W^-1/2 of the
-  // preconditioner, and the CG vectors of gdm_density_solve / gdm_coef_solve,
-  // all device memory allocated when the density is set
-  struct Density {
-    bool active = false;
-    int n_terms = 0;
-    gdmk::VarMassArgs args{};  // src / dst / add / c filled per apply
-    size_t lds = 0;
-    double mean = 1.0;
-    LineTables tab[3];
-    const LineTables *axis_tab[3] = {nullptr, nullptr, nullptr};
-    double *w_isqrt = nullptr;  // [n_owned]: (diag M[rho] / diag M)^-1/2 (n_terms > 1)
-    double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, K p
-    // per term and kernel axis diag(M_d[r_td]) (gdm_density_diag)
-    std::vector<std::vector<double>> band_diag;
-    // general density on the Gauss grid (gdm_op_set_density_grid): the launch
-    // plan of gdm_massgrid.hip; rq is the caller's array.  n_terms is 0, the
-    // solve is the CG with w_isqrt
-    bool grid = false;
-    gdmk::MgArgs grid_args{};  // src / dst / add / c filled per apply
-    double *mdiag = nullptr;   // [n_owned] diag(M): W of a grid density is formed from the current samples
-    const gdmk::CgAxis *grid_axes_dev = nullptr;  // the reduction's copy of grid_args.ax
-    double *grid_partial = nullptr;               // [2][1024] partial sums and bad counts of the reduction
-    double volume = 1.0;
-    int zc_auto = 0;  // mg_pick_zc of the mesh (gdm_op_set_density_grid_z_chunk restores it)
-    std::vector<void *> allocations;
-  } dens;
-  bool cut_inner = false;  // the inner operator of a cut handle
-  // load vector / Dirichlet data (gdm_add_load*, gdm_add_dirichlet_data; single
-  // rank, non-periodic): shape values times quadrature weights per category,
-  // the per-axis (sin, cos) load vectors of the rank-1 path [3][2][load_ld]
-  double *load_Sw = nullptr, *load_bvec = nullptr;
-  int load_ld = 0;
-  // fast diagonalisation (gdm_system_solve_setup): per kernel axis the tables
-  // S and S^T (row-major N x N) and lambda, the eigenvalue extremes for the
-  // host check of a solve, two scratch vectors
-  struct FastDiag {
-    bool built = false;
-    double *S[3] = {nullptr, nullptr, nullptr}, *St[3] = {nullptr, nullptr, nullptr};
-    double *lam[3] = {nullptr, nullptr, nullptr};
-    double lam_min[3] = {0, 0, 0}, lam_max[3] = {0, 0, 0};
-    double *tmp[2] = {nullptr, nullptr};
-  } fd;
-  // linear elasticity (GDM_OP_ELASTICITY): the Dirichlet-reduced 1D tables of
-  // the kernel (built by gdm_op_create), the diagonal, and the block
-  // fast-diagonalisation preconditioner (gdm_elasticity_precond_setup): per
-  // kernel axis S, S^T and per component the eigenvalues pre-scaled by w_cd
-  struct Elasticity {
-    double mu = 0.0, lambda = 0.0;
-    gdmk::ElasArgs args{};       // src / dst filled per apply
-    double *invdiag = nullptr;   // Jacobi: 1 / diag, built on first use
-    double *free_mask = nullptr; // 1 on free DoFs, 0 on constrained ones (first solve)
-    bool built = false;
-    double *S[3] = {nullptr, nullptr, nullptr}, *St[3] = {nullptr, nullptr, nullptr};
-    double *lam[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    double *tmp[2] = {nullptr, nullptr};
-    double *cg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // r, p, Ap, z, b (masked rhs)
-  } el;
-};
-
-namespace {
-
-void free_op(gdm_op *op) {
-  if (!op) return;
-  for (void *ptr : op->allocations) (void)hipFree(ptr);
-  for (void *ptr : op->field.allocations) (void)hipFree(ptr);
-  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
-  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
-  if (op->own_stream) (void)hipStreamDestroy(op->own_stream);
-  delete op;
-}
 
 // diag of the condensed mass P^T M P = kron_d diag(P_d^T M_d P_d) on the owned
 // DoFs (global lexicographic order from the owned plane range); constrained
 // rows of periodic directions 1
-std::vector<double> mass_diagonal_owned(const gdm_op *op) {
+std::vector<double> gdm_detail::mass_diagonal_owned(const gdm_op *op) {
   std::vector<double> dg[3];
   for (int d = 0; d < 3; ++d) {
     if (d >= op->dim) {
@@ -341,10 +68,60 @@ std::vector<double> mass_diagonal_owned(const gdm_op *op) {
   return out;
 }
 
-template <typename T>
-T *keep(gdm_op *op, T *ptr) {
-  op->allocations.push_back((void *)ptr);
-  return ptr;
+gdm::Band gdm_detail::identity_band(int p) {
+  gdm::Band b(1, p);
+  b(0, 0) = 1.0;
+  return b;
+}
+
+// gamma / h_min of the box Nitsche terms, h_min the smallest cell width over
+// the mesh's directions (0: no Nitsche terms)
+double gdm_detail::nitsche_over_hmin(const gdm_mesh_desc *mesh, double nitsche) {
+  if (!(nitsche > 0.0)) return 0.0;
+  double hmin = 1e300;
+  for (int e = 0; e < mesh->dim; ++e) hmin = std::min(hmin, (mesh->hi[e] - mesh->lo[e]) / mesh->n_subdivisions[e]);
+  return nitsche / hmin;
+}
+
+gdm::Band gdm_detail::mesh_mass_1d(const gdm_mesh_desc *mesh, int axis) {
+  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
+  return gdm::assemble_1d(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc).M;
+}
+
+// host-only entry points: the mesh arguments gdm_op_create would accept
+const char *gdm_detail::host_mesh_error(const gdm_mesh_desc *mesh, int axis) {
+  if (!mesh) return "mesh is NULL";
+  const int dim = mesh->dim, p = mesh->fe_degree;
+  if (dim < 1 || dim > 3) return "dim must be 1, 2 or 3";
+  if (p < 1 || p > 9 || p % 2 == 0) return "fe_degree must be odd in [1, 9]";
+  if (axis < 0 || axis >= dim) return "axis outside [0, dim)";
+  if (mesh->n_subdivisions[axis] < p) return "n_subdivisions must be >= fe_degree";
+  if (!(mesh->hi[axis] > mesh->lo[axis])) return "empty box";
+  return nullptr;
+}
+
+// host checks shared by the pure-host field functions; 0 = ok
+int gdm_detail::check_field_mesh(const gdm_mesh_desc *mesh, int axis) {
+  if (!mesh) return fail(GDM_ERR_ARG, "mesh is NULL");
+  const int dim = mesh->dim, p = mesh->fe_degree;
+  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
+  if (p < 1 || p > 9 || p % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
+  if (axis < 0 || axis >= dim) return fail(GDM_ERR_ARG, "axis outside [0, dim)");
+  if (mesh->n_subdivisions[axis] < p) return fail(GDM_ERR_ARG, "n_subdivisions must be >= fe_degree");
+  if (!(mesh->hi[axis] > mesh->lo[axis])) return fail(GDM_ERR_ARG, "empty box");
+  return GDM_OK;
+}
+
+namespace {
+
+void free_op(gdm_op *op) {
+  if (!op) return;
+  for (void *ptr : op->allocations) (void)hipFree(ptr);
+  for (void *ptr : op->field.allocations) (void)hipFree(ptr);
+  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
+  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
+  if (op->own_stream) (void)hipStreamDestroy(op->own_stream);
+  delete op;
 }
 
 // Build the row (x) or column (y, z) band table of a kernel axis in kernel
@@ -376,12 +153,6 @@ std::vector<double> interior_band(int p, int which) {
     case 7: return interior_band_t<7>(which);
     default: return interior_band_t<9>(which);
   }
-}
-
-gdm::Band identity_band(int p) {
-  gdm::Band b(1, p);
-  b(0, 0) = 1.0;
-  return b;
 }
 
 // Line-solve tables of one SPD band matrix M = L L^T (gdm_mass.hip): the v2
@@ -434,15 +205,6 @@ LineTables build_line_tables(gdm_op *op, const gdm::Band &M) {
     t.row_hi = hi;
   }
   return t;
-}
-
-// gamma / h_min of the box Nitsche terms, h_min the smallest cell width over
-// the mesh's directions (0: no Nitsche terms)
-double nitsche_over_hmin(const gdm_mesh_desc *mesh, double nitsche) {
-  if (!(nitsche > 0.0)) return 0.0;
-  double hmin = 1e300;
-  for (int e = 0; e < mesh->dim; ++e) hmin = std::min(hmin, (mesh->hi[e] - mesh->lo[e]) / mesh->n_subdivisions[e]);
-  return nitsche / hmin;
 }
 
 void build_tables(gdm_op *op) {
@@ -783,13 +545,14 @@ void build_faces(gdm_op *op) {
   keep(op, op->face_tmp);
 }
 
+}  // namespace
+
 // Output planes [zb, ze) of the owned range (3D: z planes; the full owned
 // range otherwise).  dst is the owned vector; only those planes are written.
 // tail / n_tail: inflow faces whose step 1 the stencil's workgroups run once
 // their chunk is done (v8 only); *tail_done reports whether it ran
-hipError_t launch_stencil(gdm_op *op, bool mass, const double *src, double *dst, int zb = -1, int ze = -1,
-                          const gdmk::FaceArgs *tail = nullptr, int n_tail = 0, bool *tail_done = nullptr,
-                          int zb2 = 0, int ze2 = 0) {
+hipError_t gdm_detail::launch_stencil(gdm_op *op, bool mass, const double *src, double *dst, int zb, int ze,
+                                      const gdmk::FaceArgs *tail, int n_tail, bool *tail_done, int zb2, int ze2) {
   if (tail_done) *tail_done = false;
   const gdm_layout &L = op->layout;
   gdmk::StencilArgs a{};
@@ -880,6 +643,8 @@ hipError_t launch_stencil(gdm_op *op, bool mass, const double *src, double *dst,
   if (e == hipSuccess && tail_done) *tail_done = ran;
   return e;
 }
+
+namespace {
 
 // the inflow faces' launch arguments (faces with |a.n| > 0, in face order)
 int face_args(gdm_op *op, const double *bc_values, double *dst_owned, int phase, gdmk::FaceArgs *fas) {
@@ -1039,114 +804,6 @@ int choose_zchunk(const gdm_op *op) {
   return std::max(1, zc);
 }
 
-// ---- linear elasticity (GDM_OP_ELASTICITY) ----
-
-// w[c][d]: weight of L_d in the diagonal block c of 2 mu (eps, eps) + lambda (div, div)
-void elasticity_weights(double mu, double lambda, double w[3][3]) {
-  for (int c = 0; c < 3; ++c)
-    for (int d = 0; d < 3; ++d) w[c][d] = c == d ? 2.0 * mu + lambda : mu;
-}
-
-gdm::ElasticityBands1D elasticity_bands(const gdm_mesh_desc *mesh, int d) {
-  const unsigned nc = (unsigned)mesh->n_subdivisions[d];
-  return gdm::elasticity_bands_1d(mesh->fe_degree, nc, (mesh->hi[d] - mesh->lo[d]) / nc);
-}
-
-// the kernel's table of one direction: [4][N][2p+1] in the order M, C, C^T, L
-std::vector<double> elasticity_table(const gdm::ElasticityBands1D &b) {
-  std::vector<double> t;
-  t.reserve(4 * b.M.a.size());
-  for (const gdm::Band *f : {&b.M, &b.C, &b.Ct, &b.L}) t.insert(t.end(), f->a.begin(), f->a.end());
-  return t;
-}
-
-// diag(P A P + I - P), component-major: C has a zero diagonal, so only the
-// diagonal blocks contribute, each a sum of products of 1D diagonals
-std::vector<double> elasticity_diagonal_host(const gdm_mesh_desc *mesh, double mu, double lambda) {
-  const int dim = mesh->dim;
-  double w[3][3];
-  elasticity_weights(mu, lambda, w);
-  std::vector<double> dm[3], dl[3];
-  int N[3] = {1, 1, 1};
-  for (int d = 0; d < 3; ++d) {
-    if (d >= dim) {
-      dm[d].assign(1, 1.0);
-      dl[d].assign(1, 0.0);
-      continue;
-    }
-    const gdm::ElasticityBands1D b = elasticity_bands(mesh, d);
-    N[d] = b.M.n;
-    dm[d].resize(N[d]);
-    dl[d].resize(N[d]);
-    for (int i = 0; i < N[d]; ++i) {
-      dm[d][i] = b.M(i, i);
-      dl[d][i] = b.L(i, i);
-    }
-  }
-  const int64_t n = (int64_t)N[0] * N[1] * N[2];
-  std::vector<double> out((size_t)(n * dim));
-  for (int c = 0; c < dim; ++c)
-    for (int i2 = 0; i2 < N[2]; ++i2)
-      for (int i1 = 0; i1 < N[1]; ++i1)
-        for (int i0 = 0; i0 < N[0]; ++i0) {
-          const int id[3] = {i0, i1, i2};
-          bool constrained = false;
-          for (int d = 0; d < dim; ++d) constrained = constrained || id[d] == 0 || id[d] == N[d] - 1;
-          double s = 0.0;
-          for (int d = 0; d < dim; ++d) {
-            double t = w[c][d];
-            for (int e = 0; e < dim; ++e) t *= e == d ? dl[e][id[e]] : dm[e][id[e]];
-            s += t;
-          }
-          out[(size_t)(c * n + ((int64_t)i2 * N[1] + i1) * N[0] + i0)] = constrained ? 1.0 : s;
-        }
-  return out;
-}
-
-// 1 on the free DoFs, 0 on the constrained ones, component-major
-std::vector<double> elasticity_mask_host(const gdm_op *op) {
-  const int64_t n = op->layout.n_owned;
-  std::vector<double> m((size_t)(n * op->dim));
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t id[3] = {i % op->N[0], (i / op->N[0]) % op->N[1], i / ((int64_t)op->N[0] * op->N[1])};
-    bool constrained = false;
-    for (int d = 0; d < op->dim; ++d) constrained = constrained || id[d] == 0 || id[d] == op->N[d] - 1;
-    for (int c = 0; c < op->dim; ++c) m[(size_t)(c * n + i)] = constrained ? 0.0 : 1.0;
-  }
-  return m;
-}
-
-void build_elasticity(gdm_op *op) {
-  gdmk::ElasArgs &A = op->el.args;
-  const double *tab[3] = {nullptr, nullptr, nullptr};
-  for (int d = 0; d < op->dim; ++d) tab[d] = keep(op, dev_upload(elasticity_table(elasticity_bands(&op->mesh, d))));
-  A.xtab = tab[0];
-  A.ytab = tab[1];
-  A.ztab = tab[2];
-  A.Nx = op->K[0];
-  A.Ny = op->K[1];
-  A.Nz = op->K[2];
-  A.comp_stride = op->layout.n_owned;
-  A.mu = op->el.mu;
-  A.lambda = op->el.lambda;
-  elasticity_weights(op->el.mu, op->el.lambda, A.w);
-}
-
-void elasticity_apply(gdm_op *op, const double *src, double *dst) {
-  gdmk::ElasArgs A = op->el.args;
-  A.src = src;
-  A.dst = dst;
-  hip_check(gdmk::launch_elasticity(op->p, op->dim, A, op->stream), "elasticity launch");
-}
-
-#define GDM_GUARD_BEGIN try {
-#define GDM_GUARD_END                                             \
-  }                                                               \
-  catch (const HipError &e) { return fail(GDM_ERR_HIP, e.what()); } \
-  catch (const std::bad_alloc &) { return fail(GDM_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::invalid_argument &e) { return fail(GDM_ERR_ARG, e.what()); } \
-  catch (const std::exception &e) { return fail(GDM_ERR_STATE, e.what()); }
-
 }  // namespace
 
 namespace {
@@ -1245,23 +902,6 @@ PeriodicTables1D periodic_tables_1d(const gdm::Band &M, int p) {
   r.rows_lo = best_a;
   r.rows_hi = n - best_b;
   return r;
-}
-
-gdm::Band mesh_mass_1d(const gdm_mesh_desc *mesh, int axis) {
-  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
-  return gdm::assemble_1d(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc).M;
-}
-
-// host-only entry points: the mesh arguments gdm_op_create would accept
-const char *host_mesh_error(const gdm_mesh_desc *mesh, int axis) {
-  if (!mesh) return "mesh is NULL";
-  const int dim = mesh->dim, p = mesh->fe_degree;
-  if (dim < 1 || dim > 3) return "dim must be 1, 2 or 3";
-  if (p < 1 || p > 9 || p % 2 == 0) return "fe_degree must be odd in [1, 9]";
-  if (axis < 0 || axis >= dim) return "axis outside [0, dim)";
-  if (mesh->n_subdivisions[axis] < p) return "n_subdivisions must be >= fe_degree";
-  if (!(mesh->hi[axis] > mesh->lo[axis])) return "empty box";
-  return nullptr;
 }
 
 void build_periodic_mass(gdm_op *op) {
@@ -1476,6 +1116,8 @@ void build_spike(gdm_op *op) {
     T.G0 = keep(op, dev_upload(std::vector<double>((size_t)2 * p * std::max<int64_t>(L.plane_size, 1), 0.0)));
 }
 
+}  // namespace
+
 // the line solves of M^-1 along every kernel axis; `part` replaces the
 // partitioned axis' tables by the slab's diagonal block (multi-rank), a
 // non-NULL axis_tab[ax] those of kernel axis ax at the unchanged line length
@@ -1483,8 +1125,8 @@ void build_spike(gdm_op *op) {
 // rk (single rank): the RK stage update of gdm_mass_solve_rk fused into the
 // last pass when that is the unsegmented v3 x pass; returns whether it was
 // (else x_owned holds M^-1 rhs and the caller updates)
-bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, const LineTables *part,
-                       const gdmk::RkOut *rk = nullptr, const LineTables *const *axis_tab = nullptr) {
+bool gdm_detail::mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, const LineTables *part,
+                                   const gdmk::RkOut *rk, const LineTables *const *axis_tab) {
   const int64_t n = op->layout.n_owned;
   if (n <= 0) return false;
   int64_t K[3] = {op->K[0], op->K[1], op->K[2]};
@@ -1612,8 +1254,6 @@ bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, con
     hip_check(hipMemcpyAsync(x_owned, in, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
   return false;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1852,6 +1492,8 @@ int gdm_op_use_own_stream(gdm_op *op) {
   return GDM_OK;
 }
 
+}  // extern "C"
+
 namespace {
 
 // constraints.distribute(src) into a scratch copy, the operator, then the
@@ -1869,12 +1511,16 @@ void periodic_stencil(gdm_op *op, bool mass, const double *src, double *dst) {
     if (op->mesh.periodic & (1 << d)) hip_check(gdmk_launch_periodic(dst, N, d, 1, op->stream), "condense");
 }
 
-void any_stencil(gdm_op *op, bool mass, const double *src, double *dst) {
+}  // namespace
+
+void gdm_detail::any_stencil(gdm_op *op, bool mass, const double *src, double *dst) {
   if (op->mesh.periodic)
     periodic_stencil(op, mass, src, dst);
   else
     hip_check(launch_stencil(op, mass, src, dst), "stencil launch");
 }
+
+namespace {
 
 
 // ---- separable advection field (gdm_varstencil.hip) -------------------------
@@ -1903,27 +1549,11 @@ void field_apply(gdm_op *op, const double *src, double *dst, const double *bc) {
   field_faces(op, src, dst, bc);
 }
 
-// host checks shared by the pure-host field functions; 0 = ok
-int check_field_mesh(const gdm_mesh_desc *mesh, int axis) {
-  if (!mesh) return fail(GDM_ERR_ARG, "mesh is NULL");
-  const int dim = mesh->dim, p = mesh->fe_degree;
-  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
-  if (p < 1 || p > 9 || p % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (axis < 0 || axis >= dim) return fail(GDM_ERR_ARG, "axis outside [0, dim)");
-  if (mesh->n_subdivisions[axis] < p) return fail(GDM_ERR_ARG, "n_subdivisions must be >= fe_degree");
-  if (!(mesh->hi[axis] > mesh->lo[axis])) return fail(GDM_ERR_ARG, "empty box");
-  return GDM_OK;
-}
-
 // Build the launch plan, tables and scratch of a field into `nf` (every
 // device allocation is recorded in nf.allocations as it is made).
 void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::Field &nf) {
-  const int p = op->p, W = 2 * p + 1, n1 = p + 1;
-  auto up = [&](const std::vector<double> &h) {
-    double *d = dev_upload(h);
-    nf.allocations.push_back(d);
-    return d;
-  };
+  const int p = op->p, n1 = p + 1;
+  std::vector<void *> &made = nf.allocations;
   nf.n_terms = n_terms;
   for (int t = 0; t < gdmk::VAR_MAX_TERMS; ++t) nf.scale[t] = 1.0;
   // distinct 1D tables: (direction, M or C, factor array); direction -1 = identity
@@ -1953,15 +1583,12 @@ void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::F
     return T.which ? m.C : m.M;
   };
   auto plain = [&](int id) {
-    if (!tabs[id].plain) tabs[id].plain = up(host_band(tabs[id]).a);
+    if (!tabs[id].plain) tabs[id].plain = up(made, host_band(tabs[id]).a);
     return (const double *)tabs[id].plain;
   };
   auto padded = [&](int id) {
     if (!tabs[id].padded) {
-      const gdm::Band B = host_band(tabs[id]);
-      std::vector<double> t((size_t)(B.n + 2 * p) * W, 0.0);
-      std::copy(B.a.begin(), B.a.end(), t.begin() + (size_t)p * W);
-      tabs[id].padded = up(t);
+      tabs[id].padded = up(made, padded_table(host_band(tabs[id]), 2, 0));
     }
     return (const double *)tabs[id].padded;
   };
@@ -2012,7 +1639,7 @@ void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::F
     for (const Samples &s_ : smp)
       if (s_.d == d && s_.f == f) return s_.dev + 1;
     const size_t n = (size_t)op->mesh.n_subdivisions[d] * n1 + 2;
-    smp.push_back(Samples{d, f, up(std::vector<double>(f, f + n))});
+    smp.push_back(Samples{d, f, up(made, std::vector<double>(f, f + n))});
     return smp.back().dev + 1;
   };
   std::vector<double> xq, wq;
@@ -2021,14 +1648,14 @@ void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::F
   for (int cat = 0; cat < std::max(1, p); ++cat)
     for (int l = 0; l < n1; ++l)
       for (int q = 0; q < n1; ++q) shape[((size_t)cat * n1 + l) * n1 + q] = gdm::shape_1d(p, cat, l, xq[q], 0);
-  const double *shape_dev = up(shape);
+  const double *shape_dev = up(made, shape);
   int64_t gmax = 1, tmax = 1;
   for (const Face &F : op->faces) {
     gmax = std::max(gmax, (int64_t)F.t0.Q * F.t1.Q);
     tmax = std::max(tmax, (int64_t)F.t0.n_nodes * F.t1.Q);
   }
-  double *G = up(std::vector<double>((size_t)gmax, 0.0));
-  double *T = up(std::vector<double>((size_t)tmax, 0.0));
+  double *G = up(made, std::vector<double>((size_t)gmax, 0.0));
+  double *T = up(made, std::vector<double>((size_t)tmax, 0.0));
   for (const Face &F : op->faces) {
     gdmk::VarFaceArgs f{};
     std::vector<int> fterm;
@@ -2073,572 +1700,19 @@ void build_field(gdm_op *op, int n_terms, const gdm_field_term *terms, gdm_op::F
   nf.active = true;
 }
 
+// install `nf` as the operator's field (applies in flight read the old tables)
+void install_field(gdm_op *op, gdm_op::Field &nf) {
+  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
+  for (void *ptr : op->field.allocations) (void)hipFree(ptr);
+  op->field = std::move(nf);
+}
+
 const char *kFieldPlanes = "gdm_apply_planes: not with a separable advection field (gdm_op_set_advection_field)";
 const char *kCoefPlanes = "gdm_apply_planes: not with a separable coefficient (gdm_op_set_coefficient)";
 
-// ---- separable coefficient of the wave operator (gdm_vardiff.hip) -----------
-
-void coef_apply(gdm_op *op, const double *src, double *dst) {
-  if (op->coef.grid) {
-    gdmk::CgArgs g = op->coef.grid_args;
-    g.src = src;
-    g.dst = dst;
-    hip_check(gdmk::launch_cg(op->p, g, op->stream), "grid coefficient apply launch");
-    // the box faces one after the other: they share the edge and corner columns and the scratch
-    for (const gdmk::CgFace &F : op->coef.grid_faces)
-      hip_check(gdmk_cg_face(F, src, op->coef.kappa_bc, op->coef.face_scratch, dst, op->stream),
-                "grid coefficient face launch");
-    return;
-  }
-  gdmk::DiffArgs a = op->coef.args;
-  a.src = src;
-  a.dst = dst;
-  hip_check(gdmk::launch_diff(op->p, a, op->coef.lds, op->stream), "coefficient apply launch");
-}
-
-// samples of a factor along direction d
-size_t coef_samples(const gdm_mesh_desc *mesh, int d) {
-  return (size_t)mesh->n_subdivisions[d] * (mesh->fe_degree + 1) + 2;
-}
-
-// Build the launch plan, tables and scratch of a coefficient into `nc` (every
-// device allocation is recorded in nc.allocations as it is made).
-void build_coef(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::Coef &nc) {
-  const int p = op->p, W = 2 * p + 1, n1 = p + 1;
-  auto up = [&](const std::vector<double> &h) {
-    double *d = dev_upload(h);
-    nc.allocations.push_back(d);
-    return d;
-  };
-  nc.n_terms = n_terms;
-  const double noh = nitsche_over_hmin(&op->mesh, op->nitsche);
-  // distinct device tables: (kernel axis, M or B, factor array); terms that
-  // pass the same array share them
-  struct Table {
-    int ax, which;
-    const double *f;
-    double *dev;
-  };
-  std::vector<Table> tabs;
-  auto table = [&](int ax, int which, const double *f) -> const double * {
-    const int d = op->kdir[ax];
-    if (d < 0) f = nullptr;
-    for (const Table &T : tabs)
-      if (T.ax == ax && T.which == which && T.f == f) return T.dev;
-    gdm::Band B(1, p);
-    if (d < 0) {
-      if (which == 0) B(0, 0) = 1.0;  // a trivial axis: M = (1), B = (0)
-    } else {
-      const unsigned ncell = (unsigned)op->mesh.n_subdivisions[d];
-      const double h = (op->mesh.hi[d] - op->mesh.lo[d]) / ncell;
-      B = which ? gdm::wave_band_1d_weighted(p, ncell, h, noh, f)
-                : gdm::assemble_1d_weighted(p, ncell, h, f ? f + 1 : nullptr).M;
-    }
-    // x: the plain rows; y: zero rows up to a whole tile; z: p zero rows in front and behind
-    const size_t rows = ax == 0 ? B.n : (ax == 1 ? gdmk::diff_y_rows(B.n) : B.n + 2 * p);
-    std::vector<double> t(rows * W, 0.0);
-    std::copy(B.a.begin(), B.a.end(), t.begin() + (ax == 2 ? (size_t)p * W : 0));
-    tabs.push_back(Table{ax, which, f, up(t)});
-    return tabs.back().dev;
-  };
-  gdmk::DiffArgs &a = nc.args;
-  a = gdmk::DiffArgs{};
-  a.Nx = op->K[0];
-  a.Ny = op->K[1];
-  a.Nz = op->K[2];
-  a.n_terms = n_terms;
-  for (int t = 0; t < n_terms; ++t) {
-    const double *f[3];
-    for (int ax = 0; ax < 3; ++ax) f[ax] = op->kdir[ax] < 0 ? nullptr : terms[t].factor[op->kdir[ax]];
-    a.xm[t] = table(0, 0, f[0]);
-    a.xb[t] = table(0, 1, f[0]);
-    a.ym[t] = table(1, 0, f[1]);
-    a.yb[t] = table(1, 1, f[1]);
-    a.zm[t] = table(2, 0, f[2]);
-    a.zb[t] = table(2, 1, f[2]);
-  }
-  nc.lds = gdmk::diff_lds(p, n_terms);
-  if (nc.lds > 160 * 1024) throw std::runtime_error("coefficient: the launch plan exceeds the LDS of a CU");
-  hip_check(gdmk::diff_prepare(p, nc.lds), "coefficient: LDS limit");
-
-  // the domain mean: sum_t prod_d mean(k_td), the Gauss weights sum to 1 per cell
-  std::vector<double> xq, wq;
-  gdm::gauss_unit(n1, xq, wq);
-  nc.mean = 0.0;
-  for (int t = 0; t < n_terms; ++t) {
-    double prod = 1.0;
-    for (int d = 0; d < op->dim; ++d) {
-      const double *f = terms[t].factor[d];
-      if (!f) continue;
-      const int ncell = op->mesh.n_subdivisions[d];
-      double s = 0.0;
-      for (int c = 0; c < ncell; ++c)
-        for (int q = 0; q < n1; ++q) s += wq[q] * f[1 + (size_t)c * n1 + q];
-      prod *= s / ncell;
-    }
-    nc.mean += prod;
-  }
-
-  // kappa at the boundary points: Gauss entries in the tangential directions,
-  // the lo / hi entry in the normal one
-  const int64_t nbc = op->layout.n_bc_points;
-  std::vector<double> kbc((size_t)std::max<int64_t>(nbc, 1), 0.0);
-  for (const Face &F : op->faces) {
-    const int e0 = F.t0.dim_index, e1 = F.t1.dim_index;
-    for (int t = 0; t < n_terms; ++t) {
-      const double *fn = terms[t].factor[F.d];
-      const double end = fn ? fn[F.side ? coef_samples(&op->mesh, F.d) - 1 : 0] : 1.0;
-      const double *f0 = e0 < 0 ? nullptr : terms[t].factor[e0], *f1 = e1 < 0 ? nullptr : terms[t].factor[e1];
-      for (int64_t i1 = 0; i1 < F.t1.Q; ++i1)
-        for (int64_t i0 = 0; i0 < F.t0.Q; ++i0)
-          kbc[(size_t)(F.offset + i1 * F.t0.Q + i0)] += end * (f0 ? f0[1 + i0] : 1.0) * (f1 ? f1[1 + i1] : 1.0);
-    }
-  }
-  nc.kappa_bc = up(kbc);
-  nc.g_scaled = up(std::vector<double>(kbc.size(), 0.0));
-  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
-  for (double *&v : nc.cg) v = up(std::vector<double>(n, 0.0));
-  nc.active = true;
-}
-
-// ---- general coefficient on the Gauss grid (gdm_coefgrid.hip) ---------------
-
-// the kernel's tables of one direction: per Gauss point the first node of the
-// cell's DoF box, the p + 1 basis values and physical derivatives, w_q h
-struct CoefGridTables {
-  std::vector<int32_t> first;
-  std::vector<double> val, der, w;
-};
-void coef_grid_tables(int p, unsigned ncell, double h, CoefGridTables &T) {
-  const int n1 = p + 1;
-  std::vector<double> xq, wq;
-  gdm::gauss_unit(n1, xq, wq);
-  const size_t Q = (size_t)ncell * n1;
-  T.first.resize(Q);
-  T.w.resize(Q);
-  T.val.resize(Q * n1);
-  T.der.resize(Q * n1);
-  for (unsigned c = 0; c < ncell; ++c) {
-    const int cat = (int)gdm::category(c, (unsigned)p, ncell), off = (int)gdm::box_offset(c, (unsigned)p, ncell);
-    for (int q = 0; q < n1; ++q) {
-      const size_t g = (size_t)c * n1 + q;
-      T.first[g] = off;
-      T.w[g] = wq[q] * h;
-      for (int i = 0; i < n1; ++i) {
-        T.val[g * n1 + i] = gdm::shape_1d(p, cat, i, xq[q], 0);
-        T.der[g * n1 + i] = gdm::shape_1d(p, cat, i, xq[q], 1) / h;
-      }
-    }
-  }
-}
-
-// The kernel axes of the tensor Gauss grid (gdm_coefgrid.hip, gdm_massgrid.hip)
-// into ax[3], every uploaded table recorded in `allocations`; a tile's footprint
-// is checked against the kernel's compile-time bounds (tile, Gauss points and
-// node span of kernel axes x and y).  Returns the volume of the box.
-double build_grid_axes(gdm_op *op, const int tile[2], const int nq_max[2], const int span_max[2], const char *what,
-                       std::vector<void *> &allocations, gdmk::CgAxis ax[3]) {
-  const int p = op->p, n1 = p + 1;
-  auto up = [&](const auto &h) {
-    auto *d = dev_upload(h);
-    allocations.push_back((void *)d);
-    return d;
-  };
-  double volume = 1.0;
-  for (int k = 0; k < 3; ++k) {
-    const int d = op->kdir[k];
-    CoefGridTables T;
-    int N = 1;
-    if (d < 0) {
-      T.first.assign(1, 0);
-      T.w.assign(1, 1.0);
-      T.val.assign((size_t)n1, 0.0);
-      T.der.assign((size_t)n1, 0.0);
-      T.val[0] = 1.0;
-    } else {
-      const unsigned ncell = (unsigned)op->mesh.n_subdivisions[d];
-      coef_grid_tables(p, ncell, (op->mesh.hi[d] - op->mesh.lo[d]) / ncell, T);
-      N = op->N[d];
-      volume *= op->mesh.hi[d] - op->mesh.lo[d];
-    }
-    const int Q = (int)T.first.size();
-    // the Gauss points whose box holds node i: a contiguous range (the boxes move monotonically)
-    std::vector<int32_t> qlo((size_t)N, Q), qhi((size_t)N, 0);
-    for (int q = 0; q < Q; ++q)
-      for (int i = T.first[q]; i <= std::min(N - 1, T.first[q] + p); ++i) {
-        qlo[(size_t)i] = std::min(qlo[(size_t)i], q);
-        qhi[(size_t)i] = std::max(qhi[(size_t)i], q + 1);
-      }
-    // the kernel's compile-time bounds on a tile's footprint
-    for (int i0 = 0; i0 < N && k < 2; i0 += tile[k]) {
-      const int il = std::min(N, i0 + tile[k]) - 1;
-      const int q0 = qlo[(size_t)i0], q1 = qhi[(size_t)il];
-      const int span = std::min(T.first[(size_t)q1 - 1] + p, N - 1) - T.first[(size_t)q0] + 1;
-      if (q1 <= q0 || q1 - q0 > nq_max[k] || span > span_max[k])
-        throw std::runtime_error(std::string(what) + ": a tile's footprint exceeds the kernel's bounds");
-    }
-    gdmk::CgAxis &A = ax[k];
-    A.N = N;
-    A.Q = Q;
-    A.first = up(T.first);
-    A.val = up(T.val);
-    A.der = up(T.der);
-    A.w = up(T.w);
-    A.qlo = up(qlo);
-    A.qhi = up(qhi);
-  }
-  return volume;
-}
-
-// Build the launch plan, tables and scratch of a grid coefficient into `nc`,
-// and run the reduction over kq (and kbc): false = a sample is not finite or
-// not positive.
-bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Coef &nc) {
-  const int p = op->p, n1 = p + 1;
-  auto up = [&](const auto &h) {
-    auto *d = dev_upload(h);
-    nc.allocations.push_back((void *)d);
-    return d;
-  };
-  nc.grid = true;
-  gdmk::CgArgs &a = nc.grid_args;
-  a = gdmk::CgArgs{};
-  a.kq = kq;
-  const int tile[2] = {gdmk::cg_tx(p), gdmk::cg_ty(p)}, nq_max[2] = {gdmk::cg_nqx(p), gdmk::cg_nqy(p)},
-            span_max[2] = {gdmk::cg_sx(p), gdmk::cg_sy(p)};
-  const double volume = build_grid_axes(op, tile, nq_max, span_max, "grid coefficient", nc.allocations, a.ax);
-  hip_check(gdmk::cg_prepare(p), "grid coefficient: LDS limit");
-
-  // the box faces (Nitsche part)
-  const int64_t nbc = op->layout.n_bc_points;
-  int64_t max_face = 1;
-  if (op->nitsche > 0.0) {
-    const int64_t stride[3] = {1, op->N[0], (int64_t)op->N[0] * op->N[1]};
-    auto axis_of = [&](int e) {  // kernel axis of reference direction e (-1: any trivial axis)
-      for (int k = 0; k < 3; ++k)
-        if (op->kdir[k] == e) return k;
-      throw std::runtime_error("grid coefficient: direction without a kernel axis");
-    };
-    for (const Face &F : op->faces) {
-      gdmk::CgFace f{};
-      const gdmk::CgAxis &A0 = a.ax[axis_of(F.t0.dim_index)], &A1 = a.ax[axis_of(F.t1.dim_index)];
-      f.n0 = F.t0.n_nodes;
-      f.n1 = F.t1.n_nodes;
-      f.Q0 = F.t0.Q;
-      f.Q1 = F.t1.Q;
-      f.nk = n1;
-      f.first0 = A0.first;
-      f.val0 = A0.val;
-      f.first1 = A1.first;
-      f.val1 = A1.val;
-      f.qs0 = F.t0.qs;
-      f.qc0 = F.t0.qc;
-      f.w0 = F.t0.w;
-      f.wmax0 = F.t0.wmax;
-      f.qs1 = F.t1.qs;
-      f.qc1 = F.t1.qc;
-      f.w1 = F.t1.w;
-      f.wmax1 = F.t1.wmax;
-      f.stride0 = F.t0.stride;
-      f.stride1 = F.t1.stride;
-      f.stride_d = stride[F.d];
-      f.base = (F.side ? (int64_t)(op->N[F.d] - 1 - p) : 0) * stride[F.d];
-      f.goff = F.offset;
-      f.gamma = nitsche_over_hmin(&op->mesh, op->nitsche);
-      const unsigned ncd = (unsigned)op->mesh.n_subdivisions[F.d];
-      const double hd = (op->mesh.hi[F.d] - op->mesh.lo[F.d]) / ncd;
-      const int cat = F.side ? (int)gdm::category(ncd - 1, (unsigned)p, ncd) : 0;
-      const double xs = F.side ? 1.0 : 0.0, nrm = F.side ? 1.0 : -1.0;
-      for (int k = 0; k < n1; ++k) {
-        f.tr[k] = gdm::shape_1d(p, cat, k, xs, 0);
-        f.dk[k] = nrm * gdm::shape_1d(p, cat, k, xs, 1) / hd;
-      }
-      if (f.Q0 != A0.Q || f.Q1 != A1.Q || f.n0 != A0.N || f.n1 != A1.N)
-        throw std::runtime_error("grid coefficient: face and volume tables disagree");
-      max_face = std::max(max_face, (int64_t)f.Q0 * f.Q1);
-      nc.grid_faces.push_back(f);
-    }
-    nc.kappa_bc = const_cast<double *>(kbc);  // borrowed, read only
-    nc.g_scaled = up(std::vector<double>((size_t)std::max<int64_t>(nbc, 1), 0.0));
-    nc.face_scratch = up(std::vector<double>((size_t)(2 * max_face), 0.0));
-  }
-  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
-  for (double *&v : nc.cg) v = up(std::vector<double>(n, 0.0));
-
-  // one reduction over kq (and kbc): the Gauss-weighted mean, and the samples that are not finite or not positive
-  constexpr int blocks = 1024;
-  std::vector<gdmk::CgAxis> axes(a.ax, a.ax + 3);
-  const gdmk::CgAxis *axes_dev = up(axes);
-  double *part = up(std::vector<double>((size_t)4 * blocks, 0.0));
-  const int64_t nq = (int64_t)a.ax[0].Q * a.ax[1].Q * a.ax[2].Q;
-  hip_check(gdmk_cg_reduce(kq, nq, axes_dev, part, part + blocks, blocks, op->stream), "grid coefficient reduction");
-  const bool faces = op->nitsche > 0.0 && nbc > 0;
-  if (faces)
-    hip_check(gdmk_cg_reduce(kbc, nbc, nullptr, part + 2 * blocks, part + 3 * blocks, blocks, op->stream),
-              "grid coefficient reduction");
-  std::vector<double> host((size_t)4 * blocks);
-  hip_check(hipMemcpyAsync(host.data(), part, sizeof(double) * host.size(), hipMemcpyDeviceToHost, op->stream), "copy");
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  double sum = 0.0, bad = 0.0;
-  for (int b = 0; b < blocks; ++b) {
-    sum += host[(size_t)b];
-    bad += host[(size_t)blocks + b] + host[(size_t)3 * blocks + b];
-  }
-  nc.mean = sum / volume;
-  nc.active = true;
-  return bad == 0.0;
-}
-
-// ---- separable density of the wave operator (gdm_varmass.hip) ---------------
-
-// dst = M[rho] src (+ c * add)
-void density_apply(gdm_op *op, const double *src, double *dst, const double *add = nullptr, double c = 0.0) {
-  if (op->dens.grid) {
-    gdmk::MgArgs g = op->dens.grid_args;
-    g.src = src;
-    g.dst = dst;
-    g.add = add;
-    g.c = c;
-    hip_check(gdmk::launch_mg(op->p, g, op->stream), "grid density apply launch");
-    return;
-  }
-  gdmk::VarMassArgs a = op->dens.args;
-  a.src = src;
-  a.dst = dst;
-  a.add = add;
-  a.c = c;
-  hip_check(gdmk::launch_varmass(op->p, a, op->dens.lds, op->stream), "density apply launch");
-}
-
-// M_d[f] of reference direction d, f sampled at gdm_field_points (NULL: 1)
-void density_band(const gdm_mesh_desc *mesh, int d, const double *f, gdm::Band &M) {
-  const unsigned ncell = (unsigned)mesh->n_subdivisions[d];
-  const double h = (mesh->hi[d] - mesh->lo[d]) / ncell;
-  M = gdm::assemble_1d_weighted(mesh->fe_degree, ncell, h, f ? f + 1 : nullptr).M;
-}
-
-// Build the launch plan, tables and scratch of a density into `nd` (every
-// device allocation is recorded in nd.allocations as it is made).
-void build_density(gdm_op *op, int n_terms, const gdm_coef_term *terms, gdm_op::Density &nd) {
-  const int p = op->p, W = 2 * p + 1, n1 = p + 1;
-  auto up = [&](const std::vector<double> &h) {
-    double *d = dev_upload(h);
-    nd.allocations.push_back(d);
-    return d;
-  };
-  nd.n_terms = n_terms;
-  // distinct tables: (kernel axis, factor array); terms that pass the same
-  // array share them
-  struct Table {
-    int ax;
-    const double *f;
-    double *dev;
-    gdm::Band B;
-  };
-  std::vector<Table> tabs;
-  auto table = [&](int ax, const double *f) -> size_t {
-    const int d = op->kdir[ax];
-    if (d < 0) f = nullptr;
-    for (size_t i = 0; i < tabs.size(); ++i)
-      if (tabs[i].ax == ax && tabs[i].f == f) return i;
-    gdm::Band B = identity_band(p);
-    if (d >= 0) density_band(&op->mesh, d, f, B);
-    // x: the plain rows; y: zero rows up to a whole tile; z: p zero rows in front and behind
-    const size_t rows = ax == 0 ? B.n : (ax == 1 ? gdmk::varmass_y_rows(B.n) : B.n + 2 * p);
-    std::vector<double> t(rows * W, 0.0);
-    std::copy(B.a.begin(), B.a.end(), t.begin() + (ax == 2 ? (size_t)p * W : 0));
-    tabs.push_back(Table{ax, f, up(t), B});
-    return tabs.size() - 1;
-  };
-  gdmk::VarMassArgs &a = nd.args;
-  a = gdmk::VarMassArgs{};
-  a.Nx = op->K[0];
-  a.Ny = op->K[1];
-  a.Nz = op->K[2];
-  a.n_terms = n_terms;
-  size_t term_tab[gdmk::VMASS_MAX_TERMS][3];
-  for (int t = 0; t < n_terms; ++t) {
-    for (int ax = 0; ax < 3; ++ax)
-      term_tab[t][ax] = table(ax, op->kdir[ax] < 0 ? nullptr : terms[t].factor[op->kdir[ax]]);
-    a.xm[t] = tabs[term_tab[t][0]].dev;
-    a.ym[t] = tabs[term_tab[t][1]].dev;
-    a.zm[t] = tabs[term_tab[t][2]].dev;
-  }
-  nd.lds = gdmk::varmass_lds(p, n_terms);
-  if (nd.lds > 160 * 1024) throw std::runtime_error("density: the launch plan exceeds the LDS of a CU");
-  hip_check(gdmk::varmass_prepare(p, nd.lds), "density: LDS limit");
-
-  // the domain mean: sum_t prod_d mean(r_td), the Gauss weights sum to 1 per cell
-  std::vector<double> xq, wq;
-  gdm::gauss_unit(n1, xq, wq);
-  nd.mean = 0.0;
-  for (int t = 0; t < n_terms; ++t) {
-    double prod = 1.0;
-    for (int d = 0; d < op->dim; ++d) {
-      const double *f = terms[t].factor[d];
-      if (!f) continue;
-      const int ncell = op->mesh.n_subdivisions[d];
-      double s = 0.0;
-      for (int c = 0; c < ncell; ++c)
-        for (int q = 0; q < n1; ++q) s += wq[q] * f[1 + (size_t)c * n1 + q];
-      prod *= s / ncell;
-    }
-    nd.mean += prod;
-  }
-
-  // diag(M_d[r_td]) per term and kernel axis (gdm_density_diag)
-  nd.band_diag.assign((size_t)n_terms * 3, std::vector<double>());
-  for (int t = 0; t < n_terms; ++t)
-    for (int ax = 0; ax < 3; ++ax) {
-      std::vector<double> &v = nd.band_diag[(size_t)t * 3 + ax];
-      v.assign((size_t)op->K[ax], 1.0);
-      if (op->kdir[ax] < 0) continue;
-      const gdm::Band &B = tabs[term_tab[t][ax]].B;
-      for (int i = 0; i < op->K[ax]; ++i) v[(size_t)i] = B(i, i);
-    }
-
-  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
-  if (n_terms == 1) {
-    // M[rho]^-1 = (x)_d M_d[r_d]^-1: the two-sweep line tables of every factor;
-    // a negative factor is factored as -M_d[r_d] (the signs multiply to +1)
-    for (int ax = 0; ax < 3; ++ax) {
-      if (op->kdir[ax] < 0) continue;
-      gdm::Band B = tabs[term_tab[0][ax]].B;
-      if (B(0, 0) < 0.0)
-        for (double &v : B.a) v = -v;
-      std::vector<double> lrow, invd;
-      gdm::cholesky_band(B, lrow, invd);
-      lrow.resize(lrow.size() + (size_t)p * (p + 1), 0.0);  // zero pad for the backward sweep
-      nd.tab[ax].lrow = up(lrow);
-      nd.tab[ax].invd = up(invd);
-      nd.axis_tab[ax] = &nd.tab[ax];
-    }
-  } else {
-    // W = diag(M[rho]) / diag(M) = sum_t prod_d diag(M_d[r_td]) / prod_d diag(M_d)
-    std::vector<std::vector<double>> dg((size_t)n_terms * 3);
-    for (int t = 0; t < n_terms; ++t)
-      for (int ax = 0; ax < 3; ++ax) {
-        std::vector<double> &v = dg[(size_t)t * 3 + ax];
-        v.assign((size_t)op->K[ax], 1.0);
-        if (op->kdir[ax] < 0) continue;
-        const gdm::Band &B = tabs[term_tab[t][ax]].B;
-        const gdm::Band M = mesh_mass_1d(&op->mesh, op->kdir[ax]);
-        for (int i = 0; i < op->K[ax]; ++i) v[(size_t)i] = B(i, i) / M(i, i);
-      }
-    std::vector<double> w(n, 1.0);
-    const int Nx = op->K[0], Ny = op->K[1], Nz = op->K[2];
-    if (op->layout.n_owned == (int64_t)Nx * Ny * Nz)
-      for (int z = 0; z < Nz; ++z)
-        for (int y = 0; y < Ny; ++y)
-          for (int x = 0; x < Nx; ++x) {
-            double s = 0.0;
-            for (int t = 0; t < n_terms; ++t)
-              s += dg[(size_t)t * 3][(size_t)x] * dg[(size_t)t * 3 + 1][(size_t)y] * dg[(size_t)t * 3 + 2][(size_t)z];
-            // a density that is not positive is the caller's error: the CG reports the breakdown
-            w[((size_t)z * Ny + y) * Nx + x] = s > 0.0 ? 1.0 / std::sqrt(s) : 1.0;
-          }
-    nd.w_isqrt = up(w);
-  }
-  for (double *&v : nd.cg) v = up(std::vector<double>(n, 0.0));
-  nd.active = true;
-}
-
-// ---- general density on the Gauss grid (gdm_massgrid.hip) -------------------
-
-// W^-1/2 = (diag M[rho] / diag M)^-1/2 of a grid density from the samples as they are
-// now: the kernel's diagonal mode into a CG vector, then the ratio (two launches)
-void density_grid_scaling(gdm_op *op, gdm_op::Density &D) {
-  gdmk::MgArgs g = D.grid_args;
-  g.dst = D.cg[2];
-  hip_check(gdmk::launch_mg_diag(op->p, g, op->stream), "grid density diagonal launch");
-  hip_check(gdmk_mg_wisqrt(op->layout.n_owned, D.cg[2], D.mdiag, D.w_isqrt, op->stream), "grid density scaling");
-}
-
-// One reduction over the samples of a grid density: the Gauss-weighted mean into
-// *mean (1024 block partials, summed here in a fixed order); false = a sample is
-// not finite or not positive
-constexpr int kGridBlocks = 1024;
-bool density_grid_reduce(gdm_op *op, const gdm_op::Density &D, double *mean) {
-  const gdmk::MgArgs &a = D.grid_args;
-  const int64_t nq = (int64_t)a.ax[0].Q * a.ax[1].Q * a.ax[2].Q;
-  hip_check(gdmk_cg_reduce(a.rq, nq, D.grid_axes_dev, D.grid_partial, D.grid_partial + kGridBlocks, kGridBlocks,
-                           op->stream), "grid density reduction");
-  std::vector<double> host((size_t)2 * kGridBlocks);
-  hip_check(hipMemcpyAsync(host.data(), D.grid_partial, sizeof(double) * host.size(), hipMemcpyDeviceToHost,
-                           op->stream), "copy");
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  double sum = 0.0, bad = 0.0;
-  for (int b = 0; b < kGridBlocks; ++b) {
-    sum += host[(size_t)b];
-    bad += host[(size_t)kGridBlocks + b];
-  }
-  *mean = sum / D.volume;
-  return bad == 0.0;
-}
-
-// Build the launch plan, tables and scratch of a grid density into `nd`, run the
-// reduction over rq (false = a sample is not finite or not positive) and form
-// W^-1/2 = (diag M[rho] / diag M)^-1/2 of the preconditioner on the device.
-bool build_density_grid(gdm_op *op, const double *rq, gdm_op::Density &nd) {
-  const int p = op->p;
-  auto up = [&](const auto &h) {
-    auto *d = dev_upload(h);
-    nd.allocations.push_back((void *)d);
-    return d;
-  };
-  nd.grid = true;
-  nd.n_terms = 0;
-  gdmk::MgArgs &a = nd.grid_args;
-  a = gdmk::MgArgs{};
-  a.rq = rq;
-  const int tile[2] = {gdmk::mg_tx(p), gdmk::mg_ty(p)}, nq_max[2] = {gdmk::mg_nqx(p), gdmk::mg_nqy(p)},
-            span_max[2] = {gdmk::mg_sx(p), gdmk::mg_sy(p)};
-  const double volume = build_grid_axes(op, tile, nq_max, span_max, "grid density", nd.allocations, a.ax);
-  if ((int64_t)a.ax[0].N * a.ax[1].N * a.ax[2].N != op->layout.n_owned)
-    throw std::runtime_error("grid density: the kernel axes do not cover the owned DoFs");
-  int n_cu = 0;
-  hip_check(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, op->device), "hipDeviceGetAttribute");
-  nd.zc_auto = a.zc = gdmk::mg_pick_zc(p, a.ax[0].N, a.ax[1].N, a.ax[2].N, n_cu);
-  hip_check(gdmk::mg_prepare(p), "grid density: LDS limit");
-  const size_t n = (size_t)std::max<int64_t>(op->layout.n_owned, 1);
-  for (double *&v : nd.cg) v = up(std::vector<double>(n, 0.0));
-  nd.w_isqrt = up(std::vector<double>(n, 1.0));
-  nd.mdiag = up(mass_diagonal_owned(op));
-
-  std::vector<gdmk::CgAxis> axes(a.ax, a.ax + 3);
-  nd.grid_axes_dev = up(axes);
-  nd.grid_partial = up(std::vector<double>((size_t)2 * kGridBlocks, 0.0));
-  nd.volume = volume;
-  double mean = 0.0;
-  if (!density_grid_reduce(op, nd, &mean)) return false;
-  nd.mean = mean;
-  density_grid_scaling(op, nd);
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  nd.active = true;
-  return true;
-}
-
-// the refusals shared by gdm_op_set_density and gdm_op_set_density_grid; 0 = ok
-int check_density_op(gdm_op *op, const char *what) {
-  const std::string w(what);
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, w + ": wave operators only");
-  if (op->cut_inner)
-    return fail(GDM_ERR_UNSUPPORTED, w + ": the cut-cell rows of a cut handle are assembled for the unit density");
-  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, w + ": single rank only");
-  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, w + ": not with periodic constraints");
-  return GDM_OK;
-}
-
-// install `nd` as the operator's density (applies in flight read the old tables)
-void install_density(gdm_op *op, gdm_op::Density &nd) {
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  for (void *ptr : op->dens.allocations) (void)hipFree(ptr);
-  op->dens = std::move(nd);
-  // the pointers into the moved-from object
-  for (int ax = 0; ax < 3; ++ax) op->dens.axis_tab[ax] = op->dens.axis_tab[ax] ? &op->dens.tab[ax] : nullptr;
-}
 }  // namespace
+
+extern "C" {
 
 int gdm_apply(gdm_op *op, const double *src_local, double *dst_owned, const double *bc_values) {
   if (!op) return fail(GDM_ERR_ARG, "op is NULL");
@@ -2766,11 +1840,8 @@ int gdm_field_matrix_1d(const gdm_mesh_desc *mesh, int axis, int which, const do
 }
 
 int gdm_field_tile(int fe_degree, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (tile_x) *tile_x = gdmk::VAR_TX;
-  if (tile_y) *tile_y = gdmk::VAR_TY;
-  if (z_chunk) *z_chunk = gdmk::VAR_ZC;
-  return GDM_OK;
+  if (int rc = check_tile_query(fe_degree)) return rc;
+  return tile_answer(gdmk::VAR_TX, gdmk::VAR_TY, gdmk::VAR_ZC, tile_x, tile_y, z_chunk);
 }
 
 int gdm_op_set_advection_field(gdm_op *op, int n_terms, const gdm_field_term *terms) {
@@ -2789,20 +1860,10 @@ int gdm_op_set_advection_field(gdm_op *op, int n_terms, const gdm_field_term *te
       return fail(GDM_ERR_ARG, "gdm_op_set_advection_field: component must be in [0, dim)");
   GDM_GUARD_BEGIN
   hip_check(hipSetDevice(op->device), "hipSetDevice");
-  gdm_op::Field nf;
-  if (n_terms > 0) {
-    try {
-      build_field(op, n_terms, terms, nf);
-    } catch (...) {
-      for (void *ptr : nf.allocations) (void)hipFree(ptr);
-      throw;
-    }
-  }
-  // applies in flight read the old tables
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  for (void *ptr : op->field.allocations) (void)hipFree(ptr);
-  op->field = std::move(nf);
-  return GDM_OK;
+  return build_and_install<gdm_op::Field>(op, n_terms > 0, [&](gdm_op::Field &nf) {
+    build_field(op, n_terms, terms, nf);
+    return true;
+  }, install_field, "");
   GDM_GUARD_END
 }
 
@@ -2811,384 +1872,6 @@ int gdm_op_set_field_scale(gdm_op *op, const double *s) {
   if (!op->field.active) return fail(GDM_ERR_STATE, "gdm_op_set_field_scale: no advection field is set");
   for (int t = 0; t < op->field.n_terms; ++t) op->field.scale[t] = s[t];
   return GDM_OK;
-}
-
-int gdm_coef_matrix_1d(const gdm_mesh_desc *mesh, double nitsche, int axis, int which, const double *f,
-                       double *band_host) {
-  if (int rc = check_field_mesh(mesh, axis)) return rc;
-  if (!band_host) return fail(GDM_ERR_ARG, "band_host is NULL");
-  if (which != 0 && which != 1) return fail(GDM_ERR_ARG, "which: 0 = M[f], 1 = B[f]");
-  if (!std::isfinite(nitsche)) return fail(GDM_ERR_ARG, "nitsche is not finite");
-  for (int d = 0; d < mesh->dim; ++d)
-    if (mesh->n_subdivisions[d] < 1 || !(mesh->hi[d] > mesh->lo[d])) return fail(GDM_ERR_ARG, "empty box");
-  GDM_GUARD_BEGIN
-  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
-  const double h = (mesh->hi[axis] - mesh->lo[axis]) / nc;
-  const gdm::Band B = which ? gdm::wave_band_1d_weighted(mesh->fe_degree, nc, h, nitsche_over_hmin(mesh, nitsche), f)
-                            : gdm::assemble_1d_weighted(mesh->fe_degree, nc, h, f ? f + 1 : nullptr).M;
-  std::copy(B.a.begin(), B.a.end(), band_host);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_coef_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
-  if (tile_x) *tile_x = gdmk::DIFF_TX;
-  if (tile_y) *tile_y = gdmk::DIFF_TY;
-  if (z_chunk) *z_chunk = gdmk::DIFF_ZC;
-  return GDM_OK;
-}
-
-int gdm_op_set_coefficient(gdm_op *op, int n_terms, const gdm_coef_term *terms) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: wave operators only");
-  if (op->cut_inner)
-    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: the cut-cell rows of a cut handle are assembled for "
-                                     "the constant coefficient");
-  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: single rank only");
-  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient: not with periodic constraints");
-  if (n_terms < 0 || n_terms > GDM_COEF_MAX_TERMS)
-    return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: n_terms must be in [0, GDM_COEF_MAX_TERMS]");
-  if (n_terms > 0 && !terms) return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: terms is NULL");
-  for (int t = 0; t < n_terms; ++t)
-    for (int d = 0; d < op->dim; ++d) {
-      const double *f = terms[t].factor[d];
-      if (!f) continue;
-      const size_t n = coef_samples(&op->mesh, d);
-      for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(f[i])) return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: a factor sample is not finite");
-        // one term: kappa > 0 needs factors that keep their sign and never vanish
-        if (n_terms == 1 && !(f[i] * f[0] > 0.0))
-          return fail(GDM_ERR_ARG, "gdm_op_set_coefficient: a factor of a one-term coefficient vanishes or changes sign");
-      }
-    }
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  gdm_op::Coef nc;
-  if (n_terms > 0) {
-    try {
-      build_coef(op, n_terms, terms, nc);
-    } catch (...) {
-      for (void *ptr : nc.allocations) (void)hipFree(ptr);
-      throw;
-    }
-  }
-  // applies in flight read the old tables
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
-  op->coef = std::move(nc);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_coef_grid_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
-  if (tile_x) *tile_x = gdmk::cg_tx(fe_degree);
-  if (tile_y) *tile_y = gdmk::cg_ty(fe_degree);
-  if (z_chunk) *z_chunk = gdmk::cg_zc(fe_degree);
-  return GDM_OK;
-}
-
-int gdm_coef_grid_tables_1d(const gdm_mesh_desc *mesh, int axis, double *val_host, double *der_host,
-                            int32_t *first_host) {
-  if (int rc = check_field_mesh(mesh, axis)) return rc;
-  if (!val_host || !der_host || !first_host) return fail(GDM_ERR_ARG, "NULL argument");
-  GDM_GUARD_BEGIN
-  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
-  CoefGridTables T;
-  coef_grid_tables(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc, T);
-  std::copy(T.val.begin(), T.val.end(), val_host);
-  std::copy(T.der.begin(), T.der.end(), der_host);
-  std::copy(T.first.begin(), T.first.end(), first_host);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_op_set_coefficient_grid(gdm_op *op, const double *kq, const double *kbc) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (op->kind != GDM_OP_WAVE) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: wave operators only");
-  if (op->cut_inner)
-    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: the cut-cell rows of a cut handle are assembled "
-                                     "for the constant coefficient");
-  if (op->mesh.n_ranks != 1) return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: single rank only");
-  if (op->mesh.periodic)
-    return fail(GDM_ERR_UNSUPPORTED, "gdm_op_set_coefficient_grid: not with periodic constraints");
-  if (kq && op->nitsche > 0.0 && op->layout.n_bc_points > 0 && !kbc)
-    return fail(GDM_ERR_ARG, "gdm_op_set_coefficient_grid: an operator with nitsche > 0 needs kbc");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  gdm_op::Coef nc;
-  bool ok = true;
-  if (kq) {
-    try {
-      ok = build_coef_grid(op, kq, kbc, nc);
-    } catch (...) {
-      for (void *ptr : nc.allocations) (void)hipFree(ptr);
-      throw;
-    }
-    if (!ok) {
-      for (void *ptr : nc.allocations) (void)hipFree(ptr);
-      return fail(GDM_ERR_ARG, "gdm_op_set_coefficient_grid: a sample of kappa is not finite or not positive");
-    }
-  }
-  // applies in flight read the old tables
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  for (void *ptr : op->coef.allocations) (void)hipFree(ptr);
-  op->coef = std::move(nc);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_density_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
-  if (tile_x) *tile_x = gdmk::VMASS_TX;
-  if (tile_y) *tile_y = gdmk::VMASS_TY;
-  if (z_chunk) *z_chunk = gdmk::VMASS_ZC;
-  return GDM_OK;
-}
-
-int gdm_density_cholesky_1d(const gdm_mesh_desc *mesh, int axis, const double *f, double *lrow_host,
-                            double *invd_host) {
-  if (const char *e = host_mesh_error(mesh, axis)) return fail(GDM_ERR_ARG, e);
-  if (!lrow_host || !invd_host) return fail(GDM_ERR_ARG, "NULL argument");
-  if (f) {
-    const size_t n = coef_samples(mesh, axis);
-    for (size_t i = 0; i < n; ++i)
-      if (!std::isfinite(f[i])) return fail(GDM_ERR_ARG, "gdm_density_cholesky_1d: a factor sample is not finite");
-  }
-  GDM_GUARD_BEGIN
-  std::vector<double> lrow, invd;
-  try {
-    gdm::Band M;
-    density_band(mesh, axis, f, M);
-    gdm::cholesky_band(M, lrow, invd);
-  } catch (const std::runtime_error &) {
-    return fail(GDM_ERR_ARG, "gdm_density_cholesky_1d: M[f] is not positive definite");
-  }
-  std::copy(lrow.begin(), lrow.end(), lrow_host);
-  std::copy(invd.begin(), invd.end(), invd_host);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_op_set_density(gdm_op *op, int n_terms, const gdm_coef_term *terms) {
-  if (int rc = check_density_op(op, "gdm_op_set_density")) return rc;
-  if (n_terms < 0 || n_terms > GDM_COEF_MAX_TERMS)
-    return fail(GDM_ERR_ARG, "gdm_op_set_density: n_terms must be in [0, GDM_COEF_MAX_TERMS]");
-  if (n_terms > 0 && !terms) return fail(GDM_ERR_ARG, "gdm_op_set_density: terms is NULL");
-  double sign = 1.0;
-  for (int t = 0; t < n_terms; ++t)
-    for (int d = 0; d < op->dim; ++d) {
-      const double *f = terms[t].factor[d];
-      if (!f) continue;
-      const size_t n = coef_samples(&op->mesh, d);
-      for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(f[i])) return fail(GDM_ERR_ARG, "gdm_op_set_density: a factor sample is not finite");
-        // one term: rho > 0 needs factors that keep their sign and never vanish
-        if (n_terms == 1 && !(f[i] * f[0] > 0.0))
-          return fail(GDM_ERR_ARG, "gdm_op_set_density: a factor of a one-term density vanishes or changes sign");
-      }
-      if (n_terms == 1 && f[0] < 0.0) sign = -sign;
-    }
-  if (sign < 0.0) return fail(GDM_ERR_ARG, "gdm_op_set_density: the one-term density is negative");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  gdm_op::Density nd;
-  if (n_terms > 0) {
-    try {
-      build_density(op, n_terms, terms, nd);
-    } catch (...) {
-      for (void *ptr : nd.allocations) (void)hipFree(ptr);
-      throw;
-    }
-  }
-  install_density(op, nd);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_density_grid_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
-  if (tile_x) *tile_x = gdmk::mg_tx(fe_degree);
-  if (tile_y) *tile_y = gdmk::mg_ty(fe_degree);
-  if (z_chunk) *z_chunk = gdmk::mg_zc(fe_degree);
-  return GDM_OK;
-}
-
-int gdm_op_set_density_grid(gdm_op *op, const double *rq) {
-  if (int rc = check_density_op(op, "gdm_op_set_density_grid")) return rc;
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  // the reduction and the diagonal run on the operator's stream behind whatever wrote rq there
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  const char *bad_sample = "gdm_op_set_density_grid: a sample of rho is not finite or not positive";
-  if (rq && op->dens.active && op->dens.grid && op->dens.grid_args.rq == rq) {
-    // the same pointer: the tables and the scratch stand, the mean and W follow the samples
-    double mean = 0.0;
-    if (!density_grid_reduce(op, op->dens, &mean)) return fail(GDM_ERR_ARG, bad_sample);
-    op->dens.mean = mean;
-    density_grid_scaling(op, op->dens);
-    hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-    return GDM_OK;
-  }
-  gdm_op::Density nd;
-  if (rq) {
-    bool ok = true;
-    try {
-      ok = build_density_grid(op, rq, nd);
-    } catch (...) {
-      for (void *ptr : nd.allocations) (void)hipFree(ptr);
-      throw;
-    }
-    if (!ok) {
-      for (void *ptr : nd.allocations) (void)hipFree(ptr);
-      return fail(GDM_ERR_ARG, bad_sample);
-    }
-  }
-  install_density(op, nd);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_op_set_density_grid_z_chunk(gdm_op *op, int z_chunk) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (!op->dens.active || !op->dens.grid)
-    return fail(GDM_ERR_STATE, "gdm_op_set_density_grid_z_chunk: no grid density is set (gdm_op_set_density_grid)");
-  if (z_chunk == 0 || z_chunk < -1 || z_chunk > gdmk::mg_zc(op->p))
-    return fail(GDM_ERR_ARG, "gdm_op_set_density_grid_z_chunk: z_chunk must be -1 or in [1, the chunk of "
-                             "gdm_density_grid_tile]");
-  op->dens.grid_args.zc = z_chunk < 0 ? op->dens.zc_auto : z_chunk;
-  return GDM_OK;
-}
-
-int gdm_density_diag(gdm_op *op, double *dst_owned) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_diag: no density is set (gdm_op_set_density[_grid])");
-  if (!dst_owned) return fail(GDM_ERR_ARG, "NULL vector");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  const gdm_op::Density &D = op->dens;
-  if (D.grid) {
-    gdmk::MgArgs g = D.grid_args;
-    g.dst = dst_owned;
-    hip_check(gdmk::launch_mg_diag(op->p, g, op->stream), "grid density diagonal launch");
-    return GDM_OK;
-  }
-  // separable: sum_t prod_d diag(M_d[r_td]), 1D tables from the set call
-  const int Nx = op->K[0], Ny = op->K[1], Nz = op->K[2];
-  std::vector<double> h((size_t)Nx * Ny * Nz);
-  for (int z = 0; z < Nz; ++z)
-    for (int y = 0; y < Ny; ++y)
-      for (int x = 0; x < Nx; ++x) {
-        double s = 0.0;
-        for (int t = 0; t < D.n_terms; ++t)
-          s += D.band_diag[(size_t)t * 3][(size_t)x] * D.band_diag[(size_t)t * 3 + 1][(size_t)y] *
-               D.band_diag[(size_t)t * 3 + 2][(size_t)z];
-        h[((size_t)z * Ny + y) * Nx + x] = s;
-      }
-  hip_check(hipMemcpyAsync(dst_owned, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, op->stream), "copy");
-  hip_check(hipStreamSynchronize(op->stream), "hipStreamSynchronize");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_density_apply(gdm_op *op, const double *src, double *dst) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_apply: no density is set (gdm_op_set_density)");
-  if (!src || !dst || src == dst) return fail(GDM_ERR_ARG, "src and dst: distinct device vectors");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  density_apply(op, src, dst);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_density_apply_add(gdm_op *op, const double *src, double c, const double *add, double *dst) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_apply_add: no density is set (gdm_op_set_density)");
-  if (!src || !dst || src == dst || add == dst) return fail(GDM_ERR_ARG, "src, add and dst: distinct device vectors");
-  if (!std::isfinite(c)) return fail(GDM_ERR_ARG, "gdm_density_apply_add: c is not finite");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  density_apply(op, src, dst, add, c);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_density_solve(gdm_op *op, const double *rhs, double *x, double rel_tol, double abs_tol, int max_it,
-                      int *its_host, double *res_host) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (!op->dens.active) return fail(GDM_ERR_STATE, "gdm_density_solve: no density is set (gdm_op_set_density)");
-  if (!rhs || !x) return fail(GDM_ERR_ARG, "NULL vector");
-  if (op->dens.n_terms != 1 && rhs == x)
-    return fail(GDM_ERR_ARG, "gdm_density_solve: a sum of terms or a grid density needs rhs != x");
-  if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  const int64_t n = op->layout.n_owned;
-  gdm_op::Density &D = op->dens;
-  if (D.n_terms == 1) {
-    // exact: M[rho]^-1 = (x)_d M_d[r_d]^-1, two-sweep line solves with the weighted factors
-    mass_solve_passes(op, rhs, x, nullptr, nullptr, D.axis_tab);
-    if (its_host) *its_host = 0;
-    if (res_host) *res_host = 0.0;
-    return GDM_OK;
-  }
-  double *r = D.cg[0], *p = D.cg[1], *Ap = D.cg[2], *z = D.cg[3];
-  // the caller may have overwritten a borrowed grid in place: W follows the samples of this solve
-  if (D.grid) density_grid_scaling(op, D);
-  auto dot = [&](const double *u, const double *v) {
-    double s = 0.0;
-    if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
-    return s;
-  };
-  // z = W^-1/2 M^-1 W^-1/2 r
-  auto precondition = [&](const double *rr, double *zz) {
-    hip_check(gdmk_launch_vmul(n, D.w_isqrt, rr, D.cg[4], op->stream), "scale");
-    mass_solve_passes(op, D.cg[4], D.cg[4], nullptr);
-    hip_check(gdmk_launch_vmul(n, D.w_isqrt, D.cg[4], zz, op->stream), "scale");
-  };
-  // SolverCG with ReductionControl(max_it, abs_tol, rel_tol), x the initial guess
-  density_apply(op, x, r);
-  hip_check(gdmk_launch_axpby(n, 1.0, rhs, -1.0, r, op->stream), "axpby");
-  double res = std::sqrt(dot(r, r));
-  const double tol = std::max(abs_tol, rel_tol * res);
-  int it = 0;
-  auto done = [&](int code, const char *msg) {
-    if (its_host) *its_host = it;
-    if (res_host) *res_host = res;
-    return code == GDM_OK ? GDM_OK : fail(code, msg);
-  };
-  if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_density_solve: the residual is not finite");
-  if (res > tol) {
-    precondition(r, z);
-    hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
-    double rz = dot(r, z);
-    while (true) {
-      if (it >= max_it) return done(GDM_ERR_STATE, "gdm_density_solve: max_it reached (SolverControl::NoConvergence)");
-      ++it;
-      density_apply(op, p, Ap);
-      const double pAp = dot(p, Ap);
-      if (!(pAp > 0.0))
-        return done(GDM_ERR_STATE, "gdm_density_solve: breakdown (p^T M[rho] p <= 0): rho must be positive on the box");
-      const double step = rz / pAp;
-      hip_check(gdmk_launch_axpby(n, step, p, 1.0, x, op->stream), "axpby");
-      hip_check(gdmk_launch_axpby(n, -step, Ap, 1.0, r, op->stream), "axpby");
-      res = std::sqrt(dot(r, r));
-      if (res <= tol) break;
-      if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_density_solve: the residual is not finite");
-      precondition(r, z);
-      const double rz_new = dot(r, z);
-      hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
-      rz = rz_new;
-    }
-  }
-  return done(GDM_OK, "");
-  GDM_GUARD_END
 }
 
 int gdm_mass_apply(gdm_op *op, const double *src_local, double *dst_owned) {
@@ -3502,11 +2185,7 @@ int gdm_mass_solve_cg(gdm_op *op, const double *rhs_owned, double *x_owned, doub
     for (double &v : inv) v = 1.0 / v;
     op->cg_invdiag = keep(op, dev_upload(inv));
   }
-  auto dot = [&](const double *a, const double *b) {
-    double r = 0.0;
-    if (gdm_vec_dot(op, n, a, b, &r) != GDM_OK) throw std::runtime_error("dot");
-    return r;
-  };
+  auto apply = [&](const double *src, double *dst) { any_stencil(op, true, src, dst); };
   auto precondition = [&](const double *r, double *z) {
     if (precond == 1)
       hip_check(gdmk_launch_vmul(n, op->cg_invdiag, r, z, op->stream), "jacobi");
@@ -3514,37 +2193,9 @@ int gdm_mass_solve_cg(gdm_op *op, const double *rhs_owned, double *x_owned, doub
       hip_check(hipMemcpyAsync(z, r, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
   };
   // SolverCG with ReductionControl(max_it, abs_tol, rel_tol): r = b - A x
-  any_stencil(op, true, x_owned, op->cg_r);
-  hip_check(gdmk_launch_axpby(n, 1.0, rhs_owned, -1.0, op->cg_r, op->stream), "axpby");
-  double res = std::sqrt(dot(op->cg_r, op->cg_r));
-  const double tol = std::max(abs_tol, rel_tol * res);
-  int it = 0;
-  if (res > tol) {
-    precondition(op->cg_r, op->cg_z);
-    hip_check(hipMemcpyAsync(op->cg_p, op->cg_z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
-    double rz = dot(op->cg_r, op->cg_z);
-    while (true) {
-      if (it >= max_it) {
-        if (its_host) *its_host = it;
-        if (res_host) *res_host = res;
-        return fail(GDM_ERR_STATE, "gdm_mass_solve_cg: max_it reached (SolverControl::NoConvergence)");
-      }
-      ++it;
-      any_stencil(op, true, op->cg_p, op->cg_Ap);
-      const double alpha = rz / dot(op->cg_p, op->cg_Ap);
-      hip_check(gdmk_launch_axpby(n, alpha, op->cg_p, 1.0, x_owned, op->stream), "axpby");
-      hip_check(gdmk_launch_axpby(n, -alpha, op->cg_Ap, 1.0, op->cg_r, op->stream), "axpby");
-      res = std::sqrt(dot(op->cg_r, op->cg_r));
-      if (res <= tol) break;
-      precondition(op->cg_r, op->cg_z);
-      const double rz_new = dot(op->cg_r, op->cg_z);
-      hip_check(gdmk_launch_axpby(n, 1.0, op->cg_z, rz_new / rz, op->cg_p, op->stream), "axpby");
-      rz = rz_new;
-    }
-  }
-  if (its_host) *its_host = it;
-  if (res_host) *res_host = res;
-  return GDM_OK;
+  const gdm::PcgResult res = device_pcg(op, n, apply, precondition, op->cg_r, op->cg_p, op->cg_Ap, op->cg_z, rhs_owned,
+                                        x_owned, rel_tol, abs_tol, max_it);
+  return finish_pcg(res, "gdm_mass_solve_cg", its_host, res_host);
   GDM_GUARD_END
 }
 
@@ -3977,531 +2628,8 @@ int gdm_load_vector_1d(const gdm_mesh_desc *mesh, int axis, const double *f, dou
 }
 
 int gdm_load_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (dim < 1 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 1, 2 or 3");
-  if (tile_x) *tile_x = gdmk::LOAD_TX;
-  if (tile_y) *tile_y = gdmk::LOAD_TY;
-  if (z_chunk) *z_chunk = gdmk::LOAD_ZC;
-  return GDM_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// shared refusals of the fast-diagonalisation entry points; 0 = ok
-int check_fastdiag_op(gdm_op *op, const char *what, bool need_setup) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (op->kind != GDM_OP_WAVE)
-    return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": wave operators only (the stiffness matrix must be symmetric)");
-  if (op->mesh.n_ranks > 1) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": single rank only");
-  if (op->mesh.periodic) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": not with periodic constraints");
-  if (op->cut_inner) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": not on the inner operator of a cut handle");
-  if (need_setup && !op->fd.built)
-    return fail(GDM_ERR_STATE, std::string(what) + ": call gdm_system_solve_setup first");
-  return GDM_OK;
-}
-
-void fastdiag_host_tables(const gdm_mesh_desc *mesh, double nitsche, int axis, std::vector<double> &S,
-                          std::vector<double> &lambda) {
-  const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
-  const double h = (mesh->hi[axis] - mesh->lo[axis]) / nc;
-  gdm::fastdiag_1d(mesh->fe_degree, nc, h, nitsche_over_hmin(mesh, nitsche), S, lambda);
-}
-
-// one pass along kernel axis ax: dst = T src, T = S (transpose 0) or S^T (1)
-gdmk::FastdiagPass fastdiag_pass(const gdm_op *op, int ax, int transpose) {
-  gdmk::FastdiagPass P{};
-  P.N = op->K[ax];
-  P.Tt = transpose ? op->fd.S[ax] : op->fd.St[ax];
-  P.K0 = op->K[0];
-  P.K1 = op->K[1];
-  if (ax == 0) {
-    P.row_form = 1;
-    P.cols = 1;
-    P.batch = (int64_t)op->K[1] * op->K[2];
-  } else {
-    P.cols = ax == 1 ? op->K[0] : (int64_t)op->K[0] * op->K[1];
-    P.batch = ax == 1 ? op->K[2] : 1;
-  }
-  return P;
-}
-
-}  // namespace
-
-extern "C" {
-
-int gdm_fastdiag_tables(const gdm_mesh_desc *mesh, double nitsche, int axis, double *S_host, double *lambda_host) {
-  if (int rc = check_field_mesh(mesh, axis)) return rc;
-  if (!S_host || !lambda_host) return fail(GDM_ERR_ARG, "S_host / lambda_host is NULL");
-  if (!std::isfinite(nitsche)) return fail(GDM_ERR_ARG, "nitsche is not finite");
-  for (int d = 0; d < mesh->dim; ++d)
-    if (mesh->n_subdivisions[d] < 1 || !(mesh->hi[d] > mesh->lo[d])) return fail(GDM_ERR_ARG, "empty box");
-  GDM_GUARD_BEGIN
-  std::vector<double> S, lambda;
-  fastdiag_host_tables(mesh, nitsche, axis, S, lambda);
-  std::copy(S.begin(), S.end(), S_host);
-  std::copy(lambda.begin(), lambda.end(), lambda_host);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_system_solve_setup(gdm_op *op) {
-  if (int rc = check_fastdiag_op(op, "gdm_system_solve_setup", false)) return rc;
-  if (op->fd.built) return GDM_OK;
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  // everything is uploaded before the handle changes: a failure leaves it as it was
-  gdm_op::FastDiag nf;
-  std::vector<void *> made;
-  auto up = [&](const std::vector<double> &h) {
-    double *d = dev_upload(h);
-    made.push_back(d);
-    return d;
-  };
-  try {
-    for (int ax = 0; ax < 3; ++ax) {
-      const int d = op->kdir[ax];
-      if (d < 0) continue;
-      std::vector<double> S, lambda;
-      fastdiag_host_tables(&op->mesh, op->nitsche, d, S, lambda);
-      const int n = (int)lambda.size();
-      std::vector<double> St((size_t)n * n);
-      for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
-      nf.S[ax] = up(S);
-      nf.St[ax] = up(St);
-      nf.lam[ax] = up(lambda);
-      nf.lam_min[ax] = lambda.front();
-      nf.lam_max[ax] = lambda.back();
-    }
-    for (int i = 0; i < 2; ++i) {
-      double *t = nullptr;
-      hip_check(hipMalloc(&t, std::max<size_t>((size_t)op->layout.n_owned, 1) * sizeof(double)), "hipMalloc");
-      made.push_back(t);
-      nf.tmp[i] = t;
-    }
-  } catch (...) {
-    for (void *ptr : made) (void)hipFree(ptr);
-    throw;
-  }
-  for (void *ptr : made) op->allocations.push_back(ptr);
-  nf.built = true;
-  op->fd = nf;
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *src_owned, double *dst_owned) {
-  if (int rc = check_fastdiag_op(op, "gdm_fastdiag_transform", true)) return rc;
-  if (!src_owned || !dst_owned) return fail(GDM_ERR_ARG, "NULL vector");
-  if (src_owned == dst_owned) return fail(GDM_ERR_ARG, "gdm_fastdiag_transform: src and dst must be distinct vectors");
-  if (axis < 0 || axis >= op->dim) return fail(GDM_ERR_ARG, "axis outside [0, dim)");
-  if (transpose != 0 && transpose != 1) return fail(GDM_ERR_ARG, "transpose must be 0 or 1");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  int ax = 0;
-  while (op->kdir[ax] != axis) ++ax;
-  hip_check(gdmk_launch_fastdiag_pass(fastdiag_pass(op, ax, transpose), src_owned, dst_owned, op->stream),
-            "fastdiag pass");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-}  // extern "C"
-
-namespace {
-
-// x = (alpha M + tau S)^-1 rhs of the constant-coefficient operator by fast
-// diagonalisation: gdm_system_solve, and the preconditioner of gdm_coef_solve
-int fastdiag_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned) {
-  // the spectrum of alpha M + tau S in the M-orthonormal eigenbasis is alpha + tau sum_d lambda_d
-  double smin = 0.0, smax = 0.0;
-  int axes[3], n_axes = 0;
-  for (int ax = 0; ax < 3; ++ax) {
-    if (op->kdir[ax] < 0) continue;
-    axes[n_axes++] = ax;
-    smin += op->fd.lam_min[ax];
-    smax += op->fd.lam_max[ax];
-  }
-  const double e0 = alpha + tau * smin, e1 = alpha + tau * smax;
-  const double lo = std::min(e0, e1), hi = std::max(e0, e1);
-  const double near0 = std::min(std::fabs(lo), std::fabs(hi)), far0 = std::max(std::fabs(lo), std::fabs(hi));
-  if ((lo <= 0.0 && hi >= 0.0) || near0 < 1e-12 * far0) {
-    char msg[320];
-    const double tiny = 1e-10 * std::max(std::fabs(smin), std::fabs(smax));
-    if (smin < -tiny)
-      std::snprintf(msg, sizeof msg,
-                    "gdm_system_solve: the stiffness matrix is indefinite (smallest eigenvalue %.6g): the Nitsche "
-                    "penalty %g is too small for degree %d; alpha M + tau S has eigenvalues in [%.6g, %.6g]",
-                    smin, op->nitsche, op->p, lo, hi);
-    else
-      std::snprintf(msg, sizeof msg,
-                    "gdm_system_solve: alpha M + tau S is singular (eigenvalues in [%.6g, %.6g]); without Nitsche "
-                    "terms the stiffness matrix has the constants in its kernel (pure Neumann problem)",
-                    lo, hi);
-    return fail(GDM_ERR_ARG, msg);
-  }
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  // forward S^T along x, y, z (the last one scales by the inverse eigenvalues),
-  // backward S along z, y, x; ping-pong between the two scratch vectors, so rhs
-  // is read by the first pass only and x written by the last only
-  const int n_pass = 2 * n_axes;
-  const double *src = rhs_owned;
-  for (int i = 0; i < n_pass; ++i) {
-    const bool fwd = i < n_axes;
-    const int ax = fwd ? axes[i] : axes[n_pass - 1 - i];
-    gdmk::FastdiagPass P = fastdiag_pass(op, ax, fwd ? 1 : 0);
-    if (i == n_axes - 1) {
-      P.scale = 1;
-      P.alpha = alpha;
-      P.tau = tau;
-      P.lam0 = op->fd.lam[0];
-      P.lam1 = op->fd.lam[1];
-      P.lam2 = op->fd.lam[2];
-    }
-    double *dst = i == n_pass - 1 ? x_owned : op->fd.tmp[i & 1];
-    hip_check(gdmk_launch_fastdiag_pass(P, src, dst, op->stream), "fastdiag pass");
-    src = dst;
-  }
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-}  // namespace
-
-extern "C" {
-
-int gdm_system_solve(gdm_op *op, double alpha, double tau, const double *rhs_owned, double *x_owned) {
-  if (int rc = check_fastdiag_op(op, "gdm_system_solve", true)) return rc;
-  if (!rhs_owned || !x_owned) return fail(GDM_ERR_ARG, "NULL vector");
-  if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_system_solve: alpha / tau is not finite");
-  if (op->coef.active)
-    return fail(GDM_ERR_STATE, "gdm_system_solve: the direct solve is the constant-coefficient one; with a "
-                               "coefficient set use gdm_coef_solve");
-  return fastdiag_solve(op, alpha, tau, rhs_owned, x_owned);
-}
-
-int gdm_coef_solve(gdm_op *op, double alpha, double tau, const double *rhs, double *x, double rel_tol, double abs_tol,
-                   int max_it, int *its_host, double *res_host) {
-  if (int rc = check_fastdiag_op(op, "gdm_coef_solve", false)) return rc;
-  const bool dens = op->dens.active;
-  if (!op->coef.active && !dens)
-    return fail(GDM_ERR_STATE, "gdm_coef_solve: no coefficient is set (gdm_op_set_coefficient)");
-  if (!op->fd.built) return fail(GDM_ERR_STATE, "gdm_coef_solve: call gdm_system_solve_setup first (the preconditioner)");
-  if (!rhs || !x || rhs == x) return fail(GDM_ERR_ARG, "rhs and x: distinct device vectors");
-  if (!std::isfinite(alpha) || !std::isfinite(tau)) return fail(GDM_ERR_ARG, "gdm_coef_solve: alpha / tau is not finite");
-  if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  const int64_t n = op->layout.n_owned;
-  // with a density its own vectors serve (a coefficient need not be set)
-  double *const *cg = dens ? op->dens.cg : op->coef.cg;
-  double *r = cg[0], *p = cg[1], *Ap = cg[2], *z = cg[3], *Mp = cg[4];
-  const double ptau = tau * (op->coef.active ? op->coef.mean : 1.0);
-  const double palpha = alpha * (dens ? op->dens.mean : 1.0);
-  auto dot = [&](const double *u, const double *v) {
-    double s = 0.0;
-    if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
-    return s;
-  };
-  // dst = (alpha M - tau K[kappa]) src
-  auto apply = [&](const double *src, double *dst) {
-    if (dens) {
-      // (alpha M[rho] - tau K) src: K src first, then the weighted mass with the
-      // fused `+ c * add`; K = K_0 (the plain stencil) without a coefficient
-      double *Ks = alpha != 0.0 ? Mp : dst;
-      if (op->coef.active)
-        coef_apply(op, src, Ks);
-      else
-        hip_check(launch_stencil(op, false, src, Ks), "stencil launch");
-      if (alpha != 0.0) {
-        density_apply(op, src, dst, Ks, -tau / alpha);
-        if (alpha != 1.0) hip_check(gdmk_launch_axpby(n, 0.0, src, alpha, dst, op->stream), "axpby");
-      } else {
-        hip_check(gdmk_launch_axpby(n, 0.0, src, -tau, dst, op->stream), "axpby");
-      }
-      return;
-    }
-    coef_apply(op, src, dst);
-    if (alpha != 0.0) {
-      any_stencil(op, true, src, Mp);
-      hip_check(gdmk_launch_axpby(n, alpha, Mp, -tau, dst, op->stream), "axpby");
-    } else {
-      hip_check(gdmk_launch_axpby(n, 0.0, src, -tau, dst, op->stream), "axpby");
-    }
-  };
-  // SolverCG with ReductionControl(max_it, abs_tol, rel_tol), x the initial
-  // guess, preconditioned by (alpha mean(rho) M - tau mean(kappa) K_0)^-1 (a mean is 1 where nothing is set)
-  apply(x, r);
-  hip_check(gdmk_launch_axpby(n, 1.0, rhs, -1.0, r, op->stream), "axpby");
-  double res = std::sqrt(dot(r, r));
-  const double tol = std::max(abs_tol, rel_tol * res);
-  int it = 0;
-  auto done = [&](int code, const char *msg) {
-    if (its_host) *its_host = it;
-    if (res_host) *res_host = res;
-    return code == GDM_OK ? GDM_OK : fail(code, msg);
-  };
-  if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_coef_solve: the residual is not finite");
-  if (res > tol) {
-    if (int rc = fastdiag_solve(op, palpha, ptau, r, z)) return rc;
-    hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
-    double rz = dot(r, z);
-    while (true) {
-      if (it >= max_it) return done(GDM_ERR_STATE, "gdm_coef_solve: max_it reached (SolverControl::NoConvergence)");
-      ++it;
-      apply(p, Ap);
-      const double pAp = dot(p, Ap);
-      if (!(pAp > 0.0))
-        return done(GDM_ERR_STATE, "gdm_coef_solve: breakdown (p^T A p <= 0): alpha M - tau K[kappa] is not positive "
-                                   "definite; kappa must be positive on the box");
-      const double step = rz / pAp;
-      hip_check(gdmk_launch_axpby(n, step, p, 1.0, x, op->stream), "axpby");
-      hip_check(gdmk_launch_axpby(n, -step, Ap, 1.0, r, op->stream), "axpby");
-      res = std::sqrt(dot(r, r));
-      if (res <= tol) break;
-      if (!std::isfinite(res)) return done(GDM_ERR_STATE, "gdm_coef_solve: the residual is not finite");
-      if (int rc = fastdiag_solve(op, palpha, ptau, r, z)) return rc;
-      const double rz_new = dot(r, z);
-      hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
-      rz = rz_new;
-    }
-  }
-  return done(GDM_OK, "");
-  GDM_GUARD_END
-}
-
-}  // extern "C"
-
-namespace {
-
-// shared refusals of the elasticity entry points; 0 = ok
-int check_elasticity_op(gdm_op *op, const char *what, bool need_setup) {
-  if (!op) return fail(GDM_ERR_ARG, "op is NULL");
-  if (op->kind != GDM_OP_ELASTICITY) return fail(GDM_ERR_UNSUPPORTED, std::string(what) + ": elasticity operators only");
-  if (need_setup && !op->el.built)
-    return fail(GDM_ERR_STATE, std::string(what) + ": call gdm_elasticity_precond_setup first");
-  return GDM_OK;
-}
-
-// z = B^-1 r, component by component: S^T along x, y, z (the last one scales by
-// 1 / sum_d w_cd lambda_d), S along z, y, x, through the two scratch vectors
-void elasticity_precond_launch(gdm_op *op, const double *r, double *z) {
-  const int64_t n = op->layout.n_owned;
-  const int n_axes = op->dim, n_pass = 2 * n_axes;
-  for (int c = 0; c < op->dim; ++c) {
-    const double *src = r + c * n;
-    for (int i = 0; i < n_pass; ++i) {
-      const bool fwd = i < n_axes;
-      const int ax = fwd ? i : n_pass - 1 - i;
-      gdmk::FastdiagPass P{};
-      P.N = op->K[ax];
-      P.Tt = fwd ? op->el.S[ax] : op->el.St[ax];
-      P.K0 = op->K[0];
-      P.K1 = op->K[1];
-      if (ax == 0) {
-        P.row_form = 1;
-        P.cols = 1;
-        P.batch = (int64_t)op->K[1] * op->K[2];
-      } else {
-        P.cols = ax == 1 ? op->K[0] : (int64_t)op->K[0] * op->K[1];
-        P.batch = ax == 1 ? op->K[2] : 1;
-      }
-      if (i == n_axes - 1) {
-        P.scale = 1;
-        P.alpha = 0.0;
-        P.tau = 1.0;
-        P.lam0 = op->el.lam[c][0];
-        P.lam1 = op->el.lam[c][1];
-        P.lam2 = op->el.lam[c][2];
-      }
-      double *dst = i == n_pass - 1 ? z + c * n : op->el.tmp[i & 1];
-      hip_check(gdmk_launch_fastdiag_pass(P, src, dst, op->stream), "fastdiag pass");
-      src = dst;
-    }
-  }
-}
-
-void elasticity_need_invdiag(gdm_op *op) {
-  if (op->el.invdiag) return;
-  std::vector<double> inv = elasticity_diagonal_host(&op->mesh, op->el.mu, op->el.lambda);
-  for (double &v : inv) v = 1.0 / v;
-  op->el.invdiag = keep(op, dev_upload(inv));
-}
-
-}  // namespace
-
-extern "C" {
-
-int gdm_elasticity_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk) {
-  if (fe_degree < 1 || fe_degree > 9 || fe_degree % 2 == 0) return fail(GDM_ERR_UNSUPPORTED, "fe_degree must be odd in [1, 9]");
-  if (dim < 2 || dim > 3) return fail(GDM_ERR_ARG, "dim must be 2 or 3");
-  if (tile_x) *tile_x = gdmk::ELAS_TX;
-  if (tile_y) *tile_y = gdmk::ELAS_TY;
-  if (z_chunk) *z_chunk = dim == 3 ? gdmk::ELAS_ZC : 1;
-  return GDM_OK;
-}
-
-int gdm_elasticity_tables_1d(const gdm_mesh_desc *mesh, int axis, double *bands_host, double *S_host,
-                             double *lambda_host) {
-  if (int rc = check_field_mesh(mesh, axis)) return rc;
-  for (int d = 0; d < mesh->dim; ++d)
-    if (mesh->n_subdivisions[d] < 1 || !(mesh->hi[d] > mesh->lo[d])) return fail(GDM_ERR_ARG, "empty box");
-  if ((S_host == nullptr) != (lambda_host == nullptr)) return fail(GDM_ERR_ARG, "S_host and lambda_host go together");
-  GDM_GUARD_BEGIN
-  if (bands_host) {
-    const std::vector<double> t = elasticity_table(elasticity_bands(mesh, axis));
-    std::copy(t.begin(), t.end(), bands_host);
-  }
-  if (S_host) {
-    const unsigned nc = (unsigned)mesh->n_subdivisions[axis];
-    std::vector<double> S, lambda;
-    gdm::elasticity_fastdiag_1d(mesh->fe_degree, nc, (mesh->hi[axis] - mesh->lo[axis]) / nc, S, lambda);
-    std::copy(S.begin(), S.end(), S_host);
-    std::copy(lambda.begin(), lambda.end(), lambda_host);
-  }
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_elasticity_diagonal(gdm_op *op, double *diag) {
-  if (int rc = check_elasticity_op(op, "gdm_elasticity_diagonal", false)) return rc;
-  if (!diag) return fail(GDM_ERR_ARG, "NULL vector");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  const std::vector<double> d = elasticity_diagonal_host(&op->mesh, op->el.mu, op->el.lambda);
-  hip_check(hipMemcpyAsync(diag, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, op->stream), "h2d");
-  hip_check(hipStreamSynchronize(op->stream), "sync");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_elasticity_precond_setup(gdm_op *op) {
-  if (int rc = check_elasticity_op(op, "gdm_elasticity_precond_setup", false)) return rc;
-  if (op->el.built) return GDM_OK;
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  // everything is uploaded before the handle changes: a failure leaves it as it was
-  gdm_op::Elasticity ne = op->el;
-  std::vector<void *> made;
-  auto up = [&](const std::vector<double> &h) {
-    double *d = dev_upload(h);
-    made.push_back(d);
-    return d;
-  };
-  try {
-    double w[3][3];
-    elasticity_weights(op->el.mu, op->el.lambda, w);
-    for (int d = 0; d < op->dim; ++d) {  // kernel axis d = reference direction d in 2D and 3D
-      const unsigned nc = (unsigned)op->mesh.n_subdivisions[d];
-      std::vector<double> S, lambda;
-      gdm::elasticity_fastdiag_1d(op->p, nc, (op->mesh.hi[d] - op->mesh.lo[d]) / nc, S, lambda);
-      const int n = (int)lambda.size();
-      std::vector<double> St((size_t)n * n);
-      for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
-      ne.S[d] = up(S);
-      ne.St[d] = up(St);
-      for (int c = 0; c < op->dim; ++c) {
-        std::vector<double> wl(lambda);
-        for (double &v : wl) v *= w[c][d];
-        ne.lam[c][d] = up(wl);
-      }
-    }
-    for (int i = 0; i < 2; ++i) {
-      double *t = nullptr;
-      hip_check(hipMalloc(&t, std::max<size_t>((size_t)op->layout.n_owned, 1) * sizeof(double)), "hipMalloc");
-      made.push_back(t);
-      ne.tmp[i] = t;
-    }
-  } catch (...) {
-    for (void *ptr : made) (void)hipFree(ptr);
-    throw;
-  }
-  for (void *ptr : made) op->allocations.push_back(ptr);
-  ne.built = true;
-  op->el = ne;
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_elasticity_precond(gdm_op *op, const double *r, double *z) {
-  if (int rc = check_elasticity_op(op, "gdm_elasticity_precond", true)) return rc;
-  if (!r || !z || r == z) return fail(GDM_ERR_ARG, "gdm_elasticity_precond: r and z are distinct device vectors");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  elasticity_precond_launch(op, r, z);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_elasticity_solve(gdm_op *op, const double *rhs, double *x, int precond, double rel_tol, double abs_tol,
-                         int max_it, int *its_host, double *res_host) {
-  if (int rc = check_elasticity_op(op, "gdm_elasticity_solve", precond == 2)) return rc;
-  if (!rhs || !x || rhs == x) return fail(GDM_ERR_ARG, "rhs and x: distinct device vectors");
-  if (precond < 0 || precond > 2) return fail(GDM_ERR_ARG, "precond: 0 none, 1 Jacobi, 2 block fast diagonalisation");
-  if (max_it < 0) return fail(GDM_ERR_ARG, "max_it < 0");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(op->device), "hipSetDevice");
-  const int64_t n = op->layout.n_owned * op->dim;
-  for (double *&v : op->el.cg)
-    if (!v) v = keep(op, dev_upload(std::vector<double>((size_t)std::max<int64_t>(n, 1), 0.0)));
-  if (!op->el.free_mask) op->el.free_mask = keep(op, dev_upload(elasticity_mask_host(op)));
-  if (precond == 1) elasticity_need_invdiag(op);
-  double *r = op->el.cg[0], *p = op->el.cg[1], *Ap = op->el.cg[2], *z = op->el.cg[3], *b = op->el.cg[4];
-  auto dot = [&](const double *u, const double *v) {
-    double s = 0.0;
-    if (gdm_vec_dot(op, n, u, v, &s) != GDM_OK) throw std::runtime_error("dot");
-    return s;
-  };
-  auto precondition = [&](const double *rr, double *zz) {
-    if (precond == 2)
-      elasticity_precond_launch(op, rr, zz);
-    else if (precond == 1)
-      hip_check(gdmk_launch_vmul(n, op->el.invdiag, rr, zz, op->stream), "jacobi");
-    else
-      hip_check(hipMemcpyAsync(zz, rr, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
-  };
-  // the constrained entries of rhs count as 0 and those of x are 0 (the zero
-  // boundary constraints); then SolverCG with ReductionControl(max_it, abs_tol,
-  // rel_tol) on P A P + I - P: r = b - A x
-  hip_check(gdmk_launch_vmul(n, op->el.free_mask, rhs, b, op->stream), "mask");
-  hip_check(gdmk_launch_vmul(n, op->el.free_mask, x, p, op->stream), "mask");
-  hip_check(hipMemcpyAsync(x, p, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
-  elasticity_apply(op, x, r);
-  hip_check(gdmk_launch_axpby(n, 1.0, b, -1.0, r, op->stream), "axpby");
-  double res = std::sqrt(dot(r, r));
-  const double tol = std::max(abs_tol, rel_tol * res);
-  int it = 0;
-  if (res > tol) {
-    precondition(r, z);
-    hip_check(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, op->stream), "copy");
-    double rz = dot(r, z);
-    while (true) {
-      if (it >= max_it) {
-        if (its_host) *its_host = it;
-        if (res_host) *res_host = res;
-        return fail(GDM_ERR_STATE, "gdm_elasticity_solve: max_it reached (SolverControl::NoConvergence)");
-      }
-      ++it;
-      elasticity_apply(op, p, Ap);
-      const double alpha = rz / dot(p, Ap);
-      hip_check(gdmk_launch_axpby(n, alpha, p, 1.0, x, op->stream), "axpby");
-      hip_check(gdmk_launch_axpby(n, -alpha, Ap, 1.0, r, op->stream), "axpby");
-      res = std::sqrt(dot(r, r));
-      if (res <= tol) break;
-      precondition(r, z);
-      const double rz_new = dot(r, z);
-      hip_check(gdmk_launch_axpby(n, 1.0, z, rz_new / rz, p, op->stream), "axpby");
-      rz = rz_new;
-    }
-  }
-  if (its_host) *its_host = it;
-  if (res_host) *res_host = res;
-  return GDM_OK;
-  GDM_GUARD_END
+  if (int rc = check_tile_query(fe_degree, dim)) return rc;
+  return tile_answer(gdmk::LOAD_TX, gdmk::LOAD_TY, gdmk::LOAD_ZC, tile_x, tile_y, z_chunk);
 }
 
 int gdm_vec_interleave(gdm_op *op, int n_components, int to_reference, const double *src, double *dst) {
@@ -4665,648 +2793,6 @@ int gdm_time_op(gdm_op *op, int which, const double *src, double *dst, const dou
   *avg_ms_host = ms / n_iter;
   return GDM_OK;
   GDM_GUARD_END
-}
-
-// ---- cut-cell systems (host assembly in gdm_cut.cpp) ----------------------
-struct gdm_cut_system;
-int gdmh_cut_poisson_create(int p, int n_sub, double lo, double hi, const double *center, double radius,
-                            int ghost_penalty, double rhs_value, double bc_value, gdm_cut_system **out, char *err,
-                            size_t err_len);
-void gdmh_cut_info(const gdm_cut_system *S, int64_t *n_rows, int64_t *nnz, int64_t *n_inside, int64_t *n_intersected);
-void gdmh_cut_arrays(const gdm_cut_system *S, const int64_t **row_ptr, const uint32_t **cols, const double **vals,
-                     const double **rhs);
-double gdmh_cut_l2_error(const gdm_cut_system *S, const double *u);
-void gdmh_cut_destroy(gdm_cut_system *S);
-
-int gdm_cut_poisson_create(int p, int n_sub, double lo, double hi, const double *center, double radius,
-                           int ghost_penalty, double rhs_value, double bc_value, gdm_cut_system **out) {
-  if (!out) return fail(GDM_ERR_ARG, "NULL argument");
-  GDM_GUARD_BEGIN
-  char err[256] = {0};
-  if (gdmh_cut_poisson_create(p, n_sub, lo, hi, center, radius, ghost_penalty, rhs_value, bc_value, out, err,
-                              sizeof(err)) != 0)
-    return fail(std::strstr(err, "not implemented") ? GDM_ERR_UNSUPPORTED : GDM_ERR_ARG, err);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_poisson_info(const gdm_cut_system *S, int64_t *n_rows, int64_t *nnz, int64_t *n_inside_cells,
-                         int64_t *n_intersected_cells) {
-  if (!S || !n_rows || !nnz || !n_inside_cells || !n_intersected_cells) return fail(GDM_ERR_ARG, "NULL argument");
-  gdmh_cut_info(S, n_rows, nnz, n_inside_cells, n_intersected_cells);
-  return GDM_OK;
-}
-
-int gdm_cut_poisson_matrix(const gdm_cut_system *S, int device, gdm_csr **A) {
-  if (!S || !A) return fail(GDM_ERR_ARG, "NULL argument");
-  int64_t n, nnz, a, b;
-  gdmh_cut_info(S, &n, &nnz, &a, &b);
-  const int64_t *rp;
-  const uint32_t *ci;
-  const double *v, *r;
-  gdmh_cut_arrays(S, &rp, &ci, &v, &r);
-  return gdm_csr_create(device, n, n, nnz, rp, ci, v, 0, A);
-}
-
-int gdm_cut_poisson_csr(const gdm_cut_system *S, int64_t *row_ptr_host, uint32_t *cols_host, double *vals_host) {
-  if (!S || !row_ptr_host || !cols_host || !vals_host) return fail(GDM_ERR_ARG, "NULL argument");
-  int64_t n, nnz, a, b;
-  gdmh_cut_info(S, &n, &nnz, &a, &b);
-  const int64_t *rp;
-  const uint32_t *ci;
-  const double *v, *r;
-  gdmh_cut_arrays(S, &rp, &ci, &v, &r);
-  std::memcpy(row_ptr_host, rp, sizeof(int64_t) * (n + 1));
-  std::memcpy(cols_host, ci, sizeof(uint32_t) * nnz);
-  std::memcpy(vals_host, v, sizeof(double) * nnz);
-  return GDM_OK;
-}
-
-int gdm_cut_poisson_rhs(const gdm_cut_system *S, double *rhs_host) {
-  if (!S || !rhs_host) return fail(GDM_ERR_ARG, "NULL argument");
-  int64_t n, nnz, a, b;
-  gdmh_cut_info(S, &n, &nnz, &a, &b);
-  const int64_t *rp;
-  const uint32_t *ci;
-  const double *v, *r;
-  gdmh_cut_arrays(S, &rp, &ci, &v, &r);
-  std::memcpy(rhs_host, r, sizeof(double) * n);
-  return GDM_OK;
-}
-
-int gdm_cut_poisson_solve(const gdm_cut_system *S, gdm_csr *A, double rel_tol, double abs_tol, int max_it,
-                          double *u_host, int *its_host, double *res_host) {
-  if (!S || !A || !u_host) return fail(GDM_ERR_ARG, "NULL argument");
-  int64_t n, nnz, a, b, m, mc, mz;
-  gdmh_cut_info(S, &n, &nnz, &a, &b);
-  if (gdm_csr_info(A, &m, &mc, &mz) != GDM_OK || m != n || mc != n) return fail(GDM_ERR_ARG, "matrix does not match the system");
-  GDM_GUARD_BEGIN
-  const int64_t *rp;
-  const uint32_t *ci;
-  const double *v, *r;
-  gdmh_cut_arrays(S, &rp, &ci, &v, &r);
-  double *bd = nullptr, *xd = nullptr;
-  hip_check(hipMalloc(&bd, sizeof(double) * std::max<int64_t>(n, 1)), "hipMalloc rhs");
-  if (hipMalloc(&xd, sizeof(double) * std::max<int64_t>(n, 1)) != hipSuccess) {
-    (void)hipFree(bd);
-    throw HipError("hipMalloc solution");
-  }
-  int rc = GDM_OK;
-  try {
-    hip_check(hipMemcpy(bd, r, sizeof(double) * n, hipMemcpyHostToDevice), "h2d rhs");
-    hip_check(hipMemset(xd, 0, sizeof(double) * n), "memset");
-    hip_check(hipDeviceSynchronize(), "sync");
-    rc = gdm_csr_cg(A, bd, xd, 0, max_it, abs_tol, rel_tol, its_host, res_host);
-    hip_check(hipDeviceSynchronize(), "sync");
-    hip_check(hipMemcpy(u_host, xd, sizeof(double) * n, hipMemcpyDeviceToHost), "d2h solution");
-  } catch (...) {
-    (void)hipFree(bd);
-    (void)hipFree(xd);
-    throw;
-  }
-  (void)hipFree(bd);
-  (void)hipFree(xd);
-  return rc;
-  GDM_GUARD_END
-}
-
-int gdm_cut_poisson_l2_error(const gdm_cut_system *S, const double *u_host, double *err) {
-  if (!S || !u_host || !err) return fail(GDM_ERR_ARG, "NULL argument");
-  GDM_GUARD_BEGIN
-  *err = gdmh_cut_l2_error(S, u_host);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_poisson_destroy(gdm_cut_system *S) {
-  gdmh_cut_destroy(S);
-  return GDM_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Cut-cell advection (include/gdm_hip.h): host assembly of the corrections
-// (gdm_cut_advection.cpp), the uncut stencil of the box, device CSR products
-// and the banded mass solve (gdm_band.hip).
-// ---------------------------------------------------------------------------
-struct gdm_cut_adv_system;
-int gdmh_cut_adv_create(int p, int n_sub, double lo, double hi, const double *level_set, const double *advection,
-                        double gamma_A, double gamma_M, int composite, gdm_cut_adv_system **out, char *err,
-                        size_t err_len);
-void gdmh_cut_adv_coupling(const gdm_cut_adv_system *S, const int64_t **rp, const uint32_t **ci, const double **v,
-                           int64_t *nnz);
-void gdmh_cut_adv_info(const gdm_cut_adv_system *S, int64_t *n_dofs, int64_t *n_bc, int64_t *cells,
-                       int64_t *bandwidth);
-void gdmh_cut_adv_arrays(const gdm_cut_adv_system *S, const int64_t **c_rp, const uint32_t **c_ci,
-                         const double **c_v, const int64_t **f_rp, const uint32_t **f_ci, const double **f_v,
-                         const double **bc_xy, const double **lband);
-void gdmh_cut_adv_zero_rows(const gdm_cut_adv_system *S, const int64_t **rows, int64_t *n);
-void gdmh_cut_adv_destroy(gdm_cut_adv_system *S);
-hipError_t gdmk_launch_zero_rows(int64_t n, const int64_t *rows, double *y, hipStream_t st);
-hipError_t gdmk_launch_csr_accum(int64_t n_rows, const int64_t *rp, const uint32_t *ci, const double *v,
-                                 const double *x, double *y, hipStream_t st);
-hipError_t gdmk_launch_band_solve(int64_t n, int64_t bw, const double *L, double *x, hipStream_t st);
-
-}  // extern "C"
-
-struct gdm_cut_advection {
-  gdm_cut_adv_system *host = nullptr;
-  gdm_op *op = nullptr;
-  int64_t n_dofs = 0, n_bc = 0, bw = 0, cells[3] = {0, 0, 0};
-  int64_t *c_rp = nullptr, *f_rp = nullptr, *zrows = nullptr, n_zrows = 0;
-  uint32_t *c_ci = nullptr, *f_ci = nullptr;
-  double *c_v = nullptr, *f_v = nullptr, *lband = nullptr;
-  int composite = 0;  // GDM_CUT_ADV_COMPOSITE: (II)'s inflow couples to the partner field (p_*)
-  int64_t *p_rp = nullptr;
-  uint32_t *p_ci = nullptr;
-  double *p_v = nullptr;
-  std::vector<double> bc_xy;
-  void release() {
-    for (void *q : {(void *)c_rp, (void *)f_rp, (void *)c_ci, (void *)f_ci, (void *)c_v, (void *)f_v, (void *)lband,
-                    (void *)zrows, (void *)p_rp, (void *)p_ci, (void *)p_v})
-      if (q) (void)hipFree(q);
-    p_rp = nullptr;
-    p_ci = nullptr;
-    p_v = nullptr;
-    zrows = nullptr;
-    c_rp = f_rp = nullptr;
-    c_ci = f_ci = nullptr;
-    c_v = f_v = lband = nullptr;
-    if (op) gdm_op_destroy(op);
-    op = nullptr;
-    if (host) gdmh_cut_adv_destroy(host);
-    host = nullptr;
-  }
-};
-
-extern "C" {
-
-int gdm_cut_advection_create(int fe_degree, int n_subdivisions, double left, double right, const double *level_set,
-                             const double *advection, double ghost_parameter_A, double ghost_parameter_M,
-                             int device, gdm_cut_advection **out) {
-  return gdm_cut_advection_create2(fe_degree, n_subdivisions, left, right, level_set, advection, ghost_parameter_A,
-                                   ghost_parameter_M, GDM_CUT_INSIDE, 0, device, out);
-}
-
-int gdm_cut_advection_create2(int fe_degree, int n_subdivisions, double left, double right, const double *level_set,
-                              const double *advection, double ghost_parameter_A, double ghost_parameter_M,
-                              int location, int flags, int device, gdm_cut_advection **out) {
-  if (!out || !level_set || !advection) return fail(GDM_ERR_ARG, "NULL argument");
-  *out = nullptr;
-  if (location != GDM_CUT_INSIDE && location != GDM_CUT_OUTSIDE)
-    return fail(GDM_ERR_ARG, "location: GDM_CUT_INSIDE or GDM_CUT_OUTSIDE");
-  if (flags & ~GDM_CUT_ADV_COMPOSITE) return fail(GDM_ERR_ARG, "flags: GDM_CUT_ADV_COMPOSITE only");
-  GDM_GUARD_BEGIN
-  auto *c = new gdm_cut_advection();
-  try {
-    char err[256] = {0};
-    // the outside field = the same assembly on the negated level set (its inside is the outside region;
-    // MeshClassifier, face parts, surface normal and ghost-penalty faces follow the sign)
-    const size_t nv = n_subdivisions >= 0 ? (size_t)(n_subdivisions + 1) * (size_t)(n_subdivisions + 1) : 0;
-    std::vector<double> ls(level_set, level_set + nv);
-    if (location == GDM_CUT_OUTSIDE)
-      for (double &v : ls) v = -v;
-    c->composite = (flags & GDM_CUT_ADV_COMPOSITE) != 0;
-    if (gdmh_cut_adv_create(fe_degree, n_subdivisions, left, right, ls.data(), advection, ghost_parameter_A,
-                            ghost_parameter_M, c->composite, &c->host, err, sizeof(err)) != 0) {
-      delete c;
-      return fail(GDM_ERR_ARG, err);
-    }
-    // the uncut box operator S: 2D advection with the same a (stencil + outflow traces)
-    gdm_mesh_desc m{};
-    m.dim = 2;
-    m.fe_degree = fe_degree;
-    m.n_subdivisions[0] = m.n_subdivisions[1] = n_subdivisions;
-    m.n_subdivisions[2] = 1;
-    m.lo[0] = m.lo[1] = left;
-    m.hi[0] = m.hi[1] = right;
-    m.hi[2] = 1.0;
-    m.n_ranks = 1;
-    m.rank = 0;
-    const int rc = gdm_op_create(&m, GDM_OP_ADVECTION, advection, 2, device, &c->op);
-    if (rc != GDM_OK) {
-      c->release();
-      delete c;
-      return rc;
-    }
-    c->op->cut_inner = true;  // the cut rows C, F are assembled for the constant field
-    gdmh_cut_adv_info(c->host, &c->n_dofs, &c->n_bc, c->cells, &c->bw);
-    const int64_t *crp, *frp;
-    const uint32_t *cci, *fci;
-    const double *cv, *fv, *xy, *lb;
-    gdmh_cut_adv_arrays(c->host, &crp, &cci, &cv, &frp, &fci, &fv, &xy, &lb);
-    const int64_t N = c->n_dofs;
-    hip_check(hipSetDevice(device), "hipSetDevice");
-    c->c_rp = dev_upload(std::vector<int64_t>(crp, crp + N + 1));
-    c->c_ci = dev_upload(std::vector<uint32_t>(cci, cci + crp[N]));
-    c->c_v = dev_upload(std::vector<double>(cv, cv + crp[N]));
-    c->f_rp = dev_upload(std::vector<int64_t>(frp, frp + N + 1));
-    c->f_ci = dev_upload(std::vector<uint32_t>(fci, fci + frp[N]));
-    c->f_v = dev_upload(std::vector<double>(fv, fv + frp[N]));
-    c->lband = dev_upload(std::vector<double>(lb, lb + N * (c->bw + 1)));
-    const int64_t *zr;
-    gdmh_cut_adv_zero_rows(c->host, &zr, &c->n_zrows);
-    if (c->n_zrows > 0) c->zrows = dev_upload(std::vector<int64_t>(zr, zr + c->n_zrows));
-    c->bc_xy.assign(xy, xy + 2 * c->n_bc);
-    if (c->composite) {
-      const int64_t *prp;
-      const uint32_t *pci;
-      const double *pv;
-      int64_t pnnz = 0;
-      gdmh_cut_adv_coupling(c->host, &prp, &pci, &pv, &pnnz);
-      // (a field the flow only leaves through the surface has no coupling entries: pci / pv may be NULL)
-      std::vector<uint32_t> ci(std::max<int64_t>(pnnz, 1), 0u);
-      std::vector<double> cv(std::max<int64_t>(pnnz, 1), 0.0);
-      if (pnnz > 0) {
-        std::copy(pci, pci + pnnz, ci.begin());
-        std::copy(pv, pv + pnnz, cv.begin());
-      }
-      c->p_rp = dev_upload(std::vector<int64_t>(prp, prp + N + 1));
-      c->p_ci = dev_upload(ci);
-      c->p_v = dev_upload(cv);
-    }
-  } catch (...) {
-    c->release();
-    delete c;
-    throw;
-  }
-  *out = c;
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_advection_info(const gdm_cut_advection *c, int64_t *n_dofs, int64_t *n_bc_points, int64_t *cells,
-                           int64_t *mass_bandwidth) {
-  if (!c || !n_dofs || !n_bc_points || !cells || !mass_bandwidth) return fail(GDM_ERR_ARG, "NULL argument");
-  *n_dofs = c->n_dofs;
-  *n_bc_points = c->n_bc;
-  for (int k = 0; k < 3; ++k) cells[k] = c->cells[k];
-  *mass_bandwidth = c->bw;
-  return GDM_OK;
-}
-
-int gdm_cut_advection_bc_points(const gdm_cut_advection *c, double *xy_host) {
-  if (!c || (c->n_bc > 0 && !xy_host)) return fail(GDM_ERR_ARG, "NULL argument");
-  std::copy(c->bc_xy.begin(), c->bc_xy.end(), xy_host);
-  return GDM_OK;
-}
-
-int gdm_cut_advection_op(gdm_cut_advection *c, gdm_op **op) {
-  if (!c || !op) return fail(GDM_ERR_ARG, "NULL argument");
-  *op = c->op;
-  return GDM_OK;
-}
-
-int gdm_cut_advection_compute_rhs(gdm_cut_advection *c, const double *u, const double *bc, double *rhs) {
-  if (!c || !u || !rhs || (c->n_bc > 0 && !bc)) return fail(GDM_ERR_ARG, "NULL argument");
-  if (u == rhs) return fail(GDM_ERR_ARG, "u and rhs must be distinct");
-  const int rc = gdm_apply(c->op, u, rhs, nullptr);  // S u (no inflow data)
-  if (rc != GDM_OK) return rc;
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  hip_check(gdmk_launch_zero_rows(c->n_zrows, c->zrows, rhs, c->op->stream), "cut rows");
-  hip_check(gdmk_launch_csr_accum(c->n_dofs, c->c_rp, c->c_ci, c->c_v, u, rhs, c->op->stream), "cut correction");
-  if (c->n_bc > 0)
-    hip_check(gdmk_launch_csr_accum(c->n_dofs, c->f_rp, c->f_ci, c->f_v, bc, rhs, c->op->stream), "inflow data");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_advection_couple(gdm_cut_advection *c, const double *u_partner, double *rhs) {
-  if (!c || !u_partner || !rhs) return fail(GDM_ERR_ARG, "NULL argument");
-  if (!c->composite) return fail(GDM_ERR_STATE, "gdm_cut_advection_couple: created without GDM_CUT_ADV_COMPOSITE");
-  if (u_partner == rhs) return fail(GDM_ERR_ARG, "u_partner and rhs must be distinct");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  hip_check(gdmk_launch_csr_accum(c->n_dofs, c->p_rp, c->p_ci, c->p_v, u_partner, rhs, c->op->stream), "coupling");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_advection_mass_solve(gdm_cut_advection *c, const double *rhs, double *x) {
-  if (!c || !rhs || !x) return fail(GDM_ERR_ARG, "NULL argument");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  if (x != rhs)
-    hip_check(hipMemcpyAsync(x, rhs, sizeof(double) * c->n_dofs, hipMemcpyDeviceToDevice, c->op->stream), "copy");
-  hip_check(gdmk_launch_band_solve(c->n_dofs, c->bw, c->lband, x, c->op->stream), "band solve");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_advection_destroy(gdm_cut_advection *c) {
-  if (!c) return GDM_OK;
-  c->release();
-  delete c;
-  return GDM_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Cut-cell wave / heat (1D and 2D; host assembly csrc/gdm_cut_wave.cpp)
-// ---------------------------------------------------------------------------
-struct gdm_cut_wave_system;
-extern "C" {
-int gdmh_cut_wave_create(int dim, int p, int n_sub, double lo, double hi, int ls_degree, const double *ls_values,
-                         int location, int flags, double gamma_M, double gamma_A, double nitsche,
-                         gdm_cut_wave_system **out, char *err, size_t err_len);
-void gdmh_cut_wave_info(const gdm_cut_wave_system *S, int64_t *n_dofs, int64_t *n_quad, int64_t *n_surface,
-                        int64_t *cells);
-void gdmh_cut_wave_csr(const gdm_cut_wave_system *S, int which, const int64_t **rp, const uint32_t **ci,
-                       const double **v);
-void gdmh_cut_wave_points(const gdm_cut_wave_system *S, const double **qx, const double **qw, const double **sx,
-                          const double **sn, const int64_t **zero_rows, int64_t *n_zero);
-void gdmh_cut_wave_destroy(gdm_cut_wave_system *S);
-int gdmh_cut_wave_splits(const gdm_cut_wave_system *S);
-int64_t gdmh_band_cholesky(int64_t n, const int64_t *rp, const uint32_t *ci, const double *v, double alpha,
-                           const int64_t *rp2, const uint32_t *ci2, const double *v2, std::vector<double> &lband);
-}
-
-// message for a failed gdmh_band_cholesky (-1: not positive definite, -2: too large)
-static std::string band_error(int64_t code, const char *what) {
-  return std::string("cut wave: ") + what +
-         (code == -2 ? ": banded factor larger than 2^28 entries (mesh too large for the dense-band solve)"
-                     : " not positive definite");
-}
-
-
-namespace {
-struct DevCsr {
-  int64_t rows = 0;
-  int64_t *rp = nullptr;
-  uint32_t *ci = nullptr;
-  double *v = nullptr;
-  void upload(const gdm_cut_wave_system *S, int which, int64_t n_rows) {
-    const int64_t *hrp;
-    const uint32_t *hci;
-    const double *hv;
-    gdmh_cut_wave_csr(S, which, &hrp, &hci, &hv);
-    rows = n_rows;
-    rp = dev_upload(std::vector<int64_t>(hrp, hrp + n_rows + 1));
-    const int64_t nnz = hrp[n_rows];
-    std::vector<uint32_t> c1(std::max<int64_t>(nnz, 1), 0);  // one padding entry for an empty matrix
-    std::vector<double> v1(c1.size(), 0.0);
-    if (nnz > 0) {
-      std::copy(hci, hci + nnz, c1.begin());
-      std::copy(hv, hv + nnz, v1.begin());
-    }
-    ci = dev_upload(c1);
-    v = dev_upload(v1);
-  }
-  void release() {
-    for (void *q : {(void *)rp, (void *)ci, (void *)v})
-      if (q) (void)hipFree(q);
-    rp = nullptr;
-    ci = nullptr;
-    v = nullptr;
-  }
-  void accum(const double *x, double *y, hipStream_t st) const {
-    hip_check(gdmk_launch_csr_accum(rows, rp, ci, v, x, y, st), "csr accumulate");
-  }
-};
-}  // namespace
-
-struct gdm_cut_wave {
-  gdm_cut_wave_system *host = nullptr;
-  gdm_op *op = nullptr;
-  int dim = 1;
-  int64_t n_dofs = 0, n_quad = 0, n_surf = 0, cells[3] = {0, 0, 0};
-  DevCsr C, Ff, Fg, E, M, X;
-  bool coupled = false;
-  int64_t *zrows = nullptr, n_zrows = 0;
-  int64_t bw_m = -1, bw_a = -1, bw_k = -1;  // -1: no factor (no mass matrix when gamma_M < 0)
-  double *lband_m = nullptr, *lband_a = nullptr, *lband_k = nullptr, dt_a = 0.0;
-  void release() {
-    for (DevCsr *q : {&C, &Ff, &Fg, &E, &M, &X}) q->release();
-    for (void *q : {(void *)zrows, (void *)lband_m, (void *)lband_a, (void *)lband_k})
-      if (q) (void)hipFree(q);
-    zrows = nullptr;
-    lband_m = lband_a = lband_k = nullptr;
-    if (op) gdm_op_destroy(op);
-    op = nullptr;
-    if (host) gdmh_cut_wave_destroy(host);
-    host = nullptr;
-  }
-};
-
-extern "C" {
-
-int gdm_cut_wave_create(int dim, int fe_degree, int n_subdivisions, double left, double right, int ls_degree,
-                        const double *ls_values, int location, int flags, double gamma_M, double gamma_A,
-                        double nitsche, int device, gdm_cut_wave **out) {
-  if (!out || !ls_values) return fail(GDM_ERR_ARG, "NULL argument");
-  *out = nullptr;
-  GDM_GUARD_BEGIN
-  auto *c = new gdm_cut_wave();
-  try {
-    char err[256] = {0};
-    if (gdmh_cut_wave_create(dim, fe_degree, n_subdivisions, left, right, ls_degree, ls_values, location, flags,
-                             gamma_M, gamma_A, nitsche, &c->host, err, sizeof(err)) != 0) {
-      delete c;
-      return fail(GDM_ERR_ARG, err);
-    }
-    // the uncut box operator S: wave -(grad v, grad u) of the box (no box Nitsche)
-    c->dim = dim;
-    gdm_mesh_desc m{};
-    m.dim = dim;
-    m.fe_degree = fe_degree;
-    for (int d = 0; d < 3; ++d) {
-      m.n_subdivisions[d] = d < dim ? n_subdivisions : 1;
-      m.lo[d] = d < dim ? left : 0.0;
-      m.hi[d] = d < dim ? right : 1.0;
-    }
-    m.n_ranks = 1;
-    m.rank = 0;
-    const int rc = gdm_op_create(&m, GDM_OP_WAVE, nullptr, 0, device, &c->op);
-    if (rc != GDM_OK) {
-      c->release();
-      delete c;
-      return rc;
-    }
-    c->op->cut_inner = true;  // the data terms of the cut system are Ff, Fg, not the box's
-    gdmh_cut_wave_info(c->host, &c->n_dofs, &c->n_quad, &c->n_surf, c->cells);
-    gdm_layout L{};
-    if (gdm_op_layout(c->op, &L) != GDM_OK || L.n_local != c->n_dofs || L.n_owned != c->n_dofs)
-      throw std::runtime_error("cut wave: the box operator's layout is not the cut system's DoF range");
-    hip_check(hipSetDevice(device), "hipSetDevice");
-    c->C.upload(c->host, 0, c->n_dofs);
-    c->Ff.upload(c->host, 1, c->n_dofs);
-    c->Fg.upload(c->host, 2, c->n_dofs);
-    c->E.upload(c->host, 3, c->n_quad);
-    c->M.upload(c->host, 4, c->n_dofs);
-    c->coupled = (flags & GDM_CUT_WAVE_COUPLED) != 0;
-    if (c->coupled) c->X.upload(c->host, 6, c->n_dofs);
-    const double *qx, *qw, *sx, *sn;
-    const int64_t *zr;
-    gdmh_cut_wave_points(c->host, &qx, &qw, &sx, &sn, &zr, &c->n_zrows);
-    if (c->n_zrows > 0) c->zrows = dev_upload(std::vector<int64_t>(zr, zr + c->n_zrows));
-    const int64_t *rp;
-    const uint32_t *ci;
-    const double *v;
-    if (gamma_M >= 0.0) {
-      gdmh_cut_wave_csr(c->host, 4, &rp, &ci, &v);
-      std::vector<double> lb;
-      c->bw_m = gdmh_band_cholesky(c->n_dofs, rp, ci, v, 0.0, nullptr, nullptr, nullptr, lb);
-      if (c->bw_m < 0) throw std::runtime_error(band_error(c->bw_m, "mass matrix"));
-      c->lband_m = dev_upload(lb);
-    }
-  } catch (...) {
-    c->release();
-    delete c;
-    throw;
-  }
-  *out = c;
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_info(const gdm_cut_wave *c, int64_t *n_dofs, int64_t *n_quad, int64_t *n_surface, int64_t *cells) {
-  if (!c || !n_dofs || !n_quad || !n_surface || !cells) return fail(GDM_ERR_ARG, "NULL argument");
-  *n_dofs = c->n_dofs;
-  *n_quad = c->n_quad;
-  *n_surface = c->n_surf;
-  for (int k = 0; k < 3; ++k) cells[k] = c->cells[k];
-  return GDM_OK;
-}
-
-int gdm_cut_wave_points(const gdm_cut_wave *c, double *qx, double *qw, double *sx, double *sn) {
-  if (!c) return fail(GDM_ERR_ARG, "NULL argument");
-  const double *hqx, *hqw, *hsx, *hsn;
-  const int64_t *zr;
-  int64_t nz;
-  gdmh_cut_wave_points(c->host, &hqx, &hqw, &hsx, &hsn, &zr, &nz);
-  if (qx) std::copy(hqx, hqx + c->n_quad * c->dim, qx);
-  if (qw) std::copy(hqw, hqw + c->n_quad, qw);
-  if (sx) std::copy(hsx, hsx + c->n_surf * c->dim, sx);
-  if (sn) std::copy(hsn, hsn + c->n_surf * c->dim, sn);
-  return GDM_OK;
-}
-
-int gdm_cut_wave_op(gdm_cut_wave *c, gdm_op **op) {
-  if (!c || !op) return fail(GDM_ERR_ARG, "NULL argument");
-  *op = c->op;
-  return GDM_OK;
-}
-
-int gdm_cut_wave_compute_rhs(gdm_cut_wave *c, const double *u, const double *fq, const double *gs, double *rhs) {
-  if (!c || !rhs) return fail(GDM_ERR_ARG, "NULL argument");
-  if (u == rhs) return fail(GDM_ERR_ARG, "u and rhs must be distinct");
-  if (u) {
-    const int rc = gdm_apply(c->op, u, rhs, nullptr);  // S u
-    if (rc != GDM_OK) return rc;
-  }
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  hipStream_t st = c->op->stream;
-  if (u) {
-    hip_check(gdmk_launch_zero_rows(c->n_zrows, c->zrows, rhs, st), "cut rows");
-    c->C.accum(u, rhs, st);
-  } else {
-    hip_check(gdmk_launch_zero(c->n_dofs, rhs, st), "zero");
-  }
-  if (fq && c->n_quad > 0) c->Ff.accum(fq, rhs, st);
-  if (gs && c->n_surf > 0) c->Fg.accum(gs, rhs, st);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_couple(gdm_cut_wave *c, const double *u_other, double *rhs) {
-  if (!c || !u_other || !rhs) return fail(GDM_ERR_ARG, "NULL argument");
-  if (!c->coupled) return fail(GDM_ERR_ARG, "gdm_cut_wave_couple: created without GDM_CUT_WAVE_COUPLED");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  c->X.accum(u_other, rhs, c->op->stream);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_mass_apply(gdm_cut_wave *c, const double *u, double *out) {
-  if (!c || !u || !out || u == out) return fail(GDM_ERR_ARG, "NULL or aliased argument");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  hip_check(gdmk_launch_zero(c->n_dofs, out, c->op->stream), "zero");
-  c->M.accum(u, out, c->op->stream);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_mass_solve(gdm_cut_wave *c, const double *rhs, double *x) {
-  if (!c || !rhs || !x) return fail(GDM_ERR_ARG, "NULL argument");
-  if (c->bw_m < 0) return fail(GDM_ERR_ARG, "gdm_cut_wave_mass_solve: no mass matrix (gamma_M < 0)");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  if (x != rhs)
-    hip_check(hipMemcpyAsync(x, rhs, sizeof(double) * c->n_dofs, hipMemcpyDeviceToDevice, c->op->stream), "copy");
-  hip_check(gdmk_launch_band_solve(c->n_dofs, c->bw_m, c->lband_m, x, c->op->stream), "band solve");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_system_solve(gdm_cut_wave *c, double dt, const double *rhs, double *x) {
-  if (!c || !rhs || !x) return fail(GDM_ERR_ARG, "NULL argument");
-  if (!(dt > 0.0)) return fail(GDM_ERR_ARG, "gdm_cut_wave_system_solve: dt must be positive");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  if (c->bw_a < 0 || dt != c->dt_a) {
-    const int64_t *rp, *rp2;
-    const uint32_t *ci, *ci2;
-    const double *v, *v2;
-    gdmh_cut_wave_csr(c->host, 4, &rp, &ci, &v);
-    gdmh_cut_wave_csr(c->host, 5, &rp2, &ci2, &v2);
-    std::vector<double> lb;
-    const int64_t bw = gdmh_band_cholesky(c->n_dofs, rp, ci, v, dt, rp2, ci2, v2, lb);
-    if (bw < 0) throw std::runtime_error(band_error(bw, "M + dt K"));
-    // the previous factor may still be read by queued solves
-    hip_check(hipStreamSynchronize(c->op->stream), "hipStreamSynchronize");
-    if (c->lband_a) (void)hipFree(c->lband_a);
-    c->lband_a = dev_upload(lb);
-    c->bw_a = bw;
-    c->dt_a = dt;
-  }
-  if (x != rhs)
-    hip_check(hipMemcpyAsync(x, rhs, sizeof(double) * c->n_dofs, hipMemcpyDeviceToDevice, c->op->stream), "copy");
-  hip_check(gdmk_launch_band_solve(c->n_dofs, c->bw_a, c->lband_a, x, c->op->stream), "band solve");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_stiffness_solve(gdm_cut_wave *c, const double *rhs, double *x) {
-  if (!c || !rhs || !x) return fail(GDM_ERR_ARG, "NULL argument");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  if (c->bw_k < 0) {
-    const int64_t *rp;
-    const uint32_t *ci;
-    const double *v;
-    gdmh_cut_wave_csr(c->host, 5, &rp, &ci, &v);
-    std::vector<double> lb;
-    const int64_t bw = gdmh_band_cholesky(c->n_dofs, rp, ci, v, 0.0, nullptr, nullptr, nullptr, lb);
-    if (bw < 0) throw std::runtime_error(band_error(bw, "stiffness matrix"));
-    c->lband_k = dev_upload(lb);
-    c->bw_k = bw;
-  }
-  if (x != rhs)
-    hip_check(hipMemcpyAsync(x, rhs, sizeof(double) * c->n_dofs, hipMemcpyDeviceToDevice, c->op->stream), "copy");
-  hip_check(gdmk_launch_band_solve(c->n_dofs, c->bw_k, c->lband_k, x, c->op->stream), "band solve");
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_eval(gdm_cut_wave *c, const double *u, double *vals) {
-  if (!c || !u || !vals) return fail(GDM_ERR_ARG, "NULL argument");
-  GDM_GUARD_BEGIN
-  hip_check(hipSetDevice(c->op->device), "hipSetDevice");
-  hip_check(gdmk_launch_zero(c->n_quad, vals, c->op->stream), "zero");
-  c->E.accum(u, vals, c->op->stream);
-  return GDM_OK;
-  GDM_GUARD_END
-}
-
-int gdm_cut_wave_destroy(gdm_cut_wave *c) {
-  if (!c) return GDM_OK;
-  c->release();
-  delete c;
-  return GDM_OK;
 }
 
 }  // extern "C"

@@ -662,8 +662,11 @@ int gdm_mass_solve_interface_rk(gdm_op *op, const double *x_local, double beta, 
  * *Problem::solve (advection/problem.h:251-261); precond 0 = identity,
  * 1 = Jacobi (diagonal of the condensed mass).  x_owned is the initial guess
  * (the reference starts from zero); *its_host = SolverControl::last_step();
- * GDM_ERR_STATE when max_it is reached.  Works with periodic constraints (the
- * condensed operator: constrained rows zero).  Single rank. */
+ * GDM_ERR_STATE when max_it is reached.  A residual norm that is not finite (a
+ * NaN in rhs_owned or x_owned) and a breakdown (p^T A p <= 0) return
+ * GDM_ERR_STATE at once, with the iteration count reached, instead of running
+ * to max_it.  Works with periodic constraints (the condensed operator:
+ * constrained rows zero).  Single rank. */
 int gdm_mass_solve_cg(gdm_op *op, const double *rhs_owned, double *x_owned, double rel_tol, double abs_tol,
                       int max_it, int precond, int *its_host, double *res_host);
 
@@ -950,7 +953,9 @@ int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *sr
  *                        rel_tol) (elasticity_01_gdm.cc:181-184), conventions of
  *                        gdm_mass_solve_cg: x is the initial guess, *its_host =
  *                        last_step, *res_host = the final residual norm,
- *                        GDM_ERR_STATE when max_it is reached.  precond: 0 none,
+ *                        GDM_ERR_STATE when max_it is reached, and at once (with
+ *                        the count reached) for a residual norm that is not
+ *                        finite or a breakdown (p^T A p <= 0).  precond: 0 none,
  *                        1 Jacobi (the reference's), 2 the block fast
  *                        diagonalisation (GDM_ERR_STATE before
  *                        gdm_elasticity_precond_setup).  Entries of rhs on

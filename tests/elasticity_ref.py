@@ -184,6 +184,8 @@ class BlockPreconditioner:
         return z
 
 
+# not vardiff_ref.pcg: this one starts from zero, has no breakdown check (the operator is positive definite), takes
+# the preconditioner as an optional callable and returns the threshold with the history; both stay
 def pcg(A, b, precond=None, rel_tol=REL_TOL, abs_tol=ABS_TOL, max_it=1000):
     """SolverCG with ReductionControl(max_it, abs_tol, rel_tol) from a zero
     start.  Returns (x, its, hist, tol): hist[k] = |r| after iteration k

@@ -248,6 +248,30 @@ def test_solve(name):
         assert res <= tol
 
 
+@pytest.mark.parametrize("precond", [0, 1, 2])
+def test_solve_stops_at_once_on_a_nan_rhs(precond):
+    """one NaN in rhs (on a free DoF): the residual is not finite, the solve
+    returns GDM_ERR_STATE with its == 0 instead of iterating max_it = 50 times"""
+    import ctypes
+
+    from gdm_amd import _capi
+
+    op = _op(_mesh(2, 1, (4, 4)), 1.0, 0.5)
+    if precond == 2:
+        op.elasticity_precond_setup()
+    b = np.ones(2 * 16)
+    b[5] = float("nan")  # vertex (1, 1) of component 0: interior
+    rhs, x = _dev(b), op.new_vector_field()
+    its, res = ctypes.c_int(-1), ctypes.c_double(0.0)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    rc = op.lib.gdm_elasticity_solve(op.h, ptr(rhs), ptr(x), precond, 1e-8, 1e-10, 50, ctypes.byref(its),
+                                     ctypes.byref(res))
+    assert rc == -5  # GDM_ERR_STATE
+    assert its.value == 0
+    assert "gdm_elasticity_solve" in _capi.last_error() and "not finite" in _capi.last_error()
+    assert np.isnan(res.value)
+
+
 def test_golden_case_end_to_end():
     """tests/elasticity_01_gdm.cc on the device: the right-hand side through
     gdm_add_load per component, the solve, gdm_error_norms_grid per component;

@@ -332,3 +332,27 @@ def test_default_dispatch_256_cubed_is_fused(ops256, p, name):
     if Y_f is not None:
         assert torch.equal(Y_f, Y_s), float((Y_f - Y_s).abs().max())
         assert not bool(torch.isnan(Y_f).any())
+
+
+# ---- 5. the CG's guards ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim,p,n", [(1, 1, 4), (2, 3, 4)])
+@pytest.mark.parametrize("precond", [0, 1])
+def test_mass_solve_cg_stops_at_once_on_a_nan_rhs(dim, p, n, precond):
+    """one NaN in rhs: the residual is not finite, gdm_mass_solve_cg returns
+    GDM_ERR_STATE with its == 0 instead of iterating max_it = 50 times"""
+    import ctypes
+
+    from gdm_amd import _capi
+
+    op = _gdm().GdmOperator(dim, p, n, 0.0, 1.0, "mass")
+    b = np.ones(op.n_owned)
+    b[op.n_owned // 2] = NAN
+    rhs, x = dev(b), op.new_vector(local=False)
+    its, res = ctypes.c_int(-1), ctypes.c_double(0.0)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    rc = op.lib.gdm_mass_solve_cg(op.h, ptr(rhs), ptr(x), 1e-8, 1e-10, 50, precond, ctypes.byref(its),
+                                  ctypes.byref(res))
+    assert rc == -5  # GDM_ERR_STATE
+    assert its.value == 0
+    assert "gdm_mass_solve_cg" in _capi.last_error() and "not finite" in _capi.last_error()
+    assert np.isnan(res.value)

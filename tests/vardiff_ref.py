@@ -217,6 +217,7 @@ def homogeneous_matrices(m, nitsche):
     return M, K
 
 
+# (elasticity_ref.pcg is a different function: zero start, no breakdown check, another return value)
 def pcg(apply_A, apply_Pinv, b, x0=None, rel_tol=1e-8, abs_tol=0.0, max_it=1000):
     """deal.II's SolverCG with ReductionControl(max_it, abs_tol, rel_tol):
     returns (x, last_step, residual norms); raises on max_it or breakdown"""
