@@ -42,7 +42,7 @@ namespace gdmk {
 template <bool WITH_Y, bool AY = false>
 __global__ void __launch_bounds__(256) rk_update2_kernel(int64_t n, double beta, const double *__restrict__ k,
                                                          const double *acc_in, double *acc_out, double alpha,
-                                                         const double *y, double *__restrict__ Y) {
+                                                         const double *y, double *Y) {
   using d2 = double __attribute__((ext_vector_type(2)));
   const int64_t n2 = n / 2, stride = (int64_t)gridDim.x * blockDim.x;
   const d2 *k2 = reinterpret_cast<const d2 *>(k), *a2 = reinterpret_cast<const d2 *>(acc_in);
@@ -59,22 +59,24 @@ __global__ void __launch_bounds__(256) rk_update2_kernel(int64_t n, double beta,
     __builtin_nontemporal_store(__builtin_elementwise_fma(bv, ki, ai), o2 + i);
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const double ki = k[n - 1];
-    if (WITH_Y) Y[n - 1] = fma(alpha, ki, y[n - 1]);
-    acc_out[n - 1] = fma(beta, ki, acc_in[n - 1]);
+    const double ki = k[n - 1], ai = acc_in[n - 1];  // both read before Y, which may be acc_in, is written
+    if (WITH_Y) Y[n - 1] = fma(alpha, ki, AY ? ai : y[n - 1]);
+    acc_out[n - 1] = fma(beta, ki, ai);
   }
 }
 
-// scalar form for unaligned vectors
+// scalar form for unaligned vectors.  A written vector may be a read one
+// (acc_out == acc_in, Y == y, and acc_in == y: gdm_hip.h), so every operand of
+// an entry is loaded before either result is stored and only k is __restrict__.
 __global__ void __launch_bounds__(256) rk_update_kernel(int64_t n, double beta, const double *__restrict__ k,
                                                         const double *acc_in, double *acc_out, double alpha,
-                                                        const double *__restrict__ y, double *__restrict__ Y) {
+                                                        const double *y, double *Y) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   if (Y) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-      const double ki = k[i];
-      acc_out[i] = fma(beta, ki, acc_in[i]);
-      Y[i] = fma(alpha, ki, y[i]);
+      const double ki = k[i], ai = acc_in[i], yi = y[i];
+      acc_out[i] = fma(beta, ki, ai);
+      Y[i] = fma(alpha, ki, yi);
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
@@ -149,9 +151,9 @@ __global__ void __launch_bounds__(256) periodic_kernel(double *v, int64_t N0, in
   }
 }
 
-// x *= w elementwise (Jacobi preconditioner application, w = 1 / diag)
-__global__ void __launch_bounds__(256) vmul_kernel(int64_t n, const double *__restrict__ w,
-                                                   const double *__restrict__ x, double *__restrict__ y) {
+// y = w .* x elementwise (Jacobi preconditioner application, w = 1 / diag).  y may be x ("x *= w") or w: each
+// entry is read and written by one lane, so no pointer is __restrict__.
+__global__ void __launch_bounds__(256) vmul_kernel(int64_t n, const double *w, const double *x, double *y) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     y[i] = w[i] * x[i];
 }

@@ -287,8 +287,29 @@ class GdmOperator:
         return v
 
     def axpby(self, a, x, b, y):
+        """y = a x + b y (gdm_vec_axpby): an operand with a zero factor is not
+        read; x may be y"""
+        if y.numel() != x.numel():
+            raise GdmError("axpby: vector sizes differ")
         check(self.lib.gdm_vec_axpby(self.h, x.numel(), float(a), _ptr(x), float(b), _ptr(y)), "gdm_vec_axpby")
         return y
+
+    def pointwise_mult(self, w, x, y):
+        """y = w .* x (gdm_vec_pointwise_mult); y may be x or w"""
+        if w.numel() != x.numel() or y.numel() != x.numel():
+            raise GdmError("pointwise_mult: vector sizes differ")
+        check(self.lib.gdm_vec_pointwise_mult(self.h, x.numel(), _ptr(w), _ptr(x), _ptr(y)),
+              "gdm_vec_pointwise_mult")
+        return y
+
+    def mass_diagonal(self, diag_owned=None):
+        """the diagonal of the (condensed) mass matrix on the owned DoFs,
+        constrained rows 1 (gdm_mass_diagonal)"""
+        if diag_owned is None:
+            diag_owned = self.new_vector(local=False)
+        self._check_sizes(None, diag_owned)
+        check(self.lib.gdm_mass_diagonal(self.h, _ptr(diag_owned)), "gdm_mass_diagonal")
+        return diag_owned
 
     def rk_update(self, beta, k, acc_in, acc_out, alpha=0.0, y=None, Y=None):
         """acc_out = acc_in + beta k; Y = y + alpha k (when Y is given), one pass"""

@@ -116,6 +116,7 @@ class DeviceVector {
     *this = 0.0;
   }
   DeviceVector &operator=(double s) {  // only 0 is meaningful, like deal.II
+    // a = b = 0: gdm_vec_axpby reads neither operand, so fresh (uninitialised) memory becomes +0
     if (n_) check(gdm_vec_axpby(op_, (int64_t)n_, 0.0, ptr_, 0.0, ptr_), "gdm_vec_axpby");
     (void)s;
     return *this;

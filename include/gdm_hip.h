@@ -674,7 +674,8 @@ int gdm_mass_solve_cg(gdm_op *op, const double *rhs_owned, double *x_owned, doub
  * owned DoFs: the PreconditionJacobi of prototypes/advection_01_gdm.cc:211
  * and the diagonal a distributed CG preconditions with (constrained rows 1). */
 int gdm_mass_diagonal(gdm_op *op, double *diag_owned);
-/* y = w .* x elementwise (a diagonal preconditioner application) */
+/* y = w .* x elementwise (a diagonal preconditioner application).  y may equal
+ * x ("x *= w") or w; partial overlap is not allowed. */
 int gdm_vec_pointwise_mult(gdm_op *op, int64_t n, const double *w, const double *x, double *y);
 /* device-to-device copy on the operator's stream */
 int gdm_memcpy_d2d(gdm_op *op, void *dst, const void *src, size_t bytes);
@@ -694,7 +695,16 @@ int gdm_constraints_distribute(gdm_op *op, double *v_owned);
 int gdm_mass_solve_lines(gdm_op *op, int axis, double *v, int64_t n_lines, int64_t stride, int64_t A, int64_t B,
                          int64_t C);
 
-/* y = a x + b y ; *result_host = x . y */
+/* gdm_vec_axpby: y = a x + b y, one fma(a, x_i, b * y_i) per entry.  An operand
+ * whose factor is zero is not read: b == 0 gives y = a x whatever y held
+ * (uninitialised memory, NaN, Inf), a == 0 gives y = b y without touching x,
+ * a == b == 0 gives y = +0 ("v = 0" on a fresh allocation).  For finite
+ * operands this differs from the fma form only in the sign of a zero result.
+ * x may equal y (y = (a + b) y in the arithmetic above); partial overlap is
+ * not allowed.  No alignment requirement: vectors that both start on a 16-byte
+ * boundary are moved in pairs, others entry by entry, with the same bits.
+ * gdm_vec_dot: *result_host = x . y (x may equal y); two calls on the same
+ * data return the same bits. */
 int gdm_vec_axpby(gdm_op *op, int64_t n, double a, const double *x, double b, double *y);
 int gdm_vec_dot(gdm_op *op, int64_t n, const double *x, const double *y, double *result_host);
 int gdm_synchronize(gdm_op *op);
@@ -709,7 +719,13 @@ int gdm_synchronize(gdm_op *op);
  *   gdm_vec_rk_update   acc_out = acc_in + beta k and, when Y != NULL,
  *                       Y = y + alpha k, in one pass (low-storage form of a
  *                       Butcher table with one nonzero a_ij per stage, e.g.
- *                       RK_CLASSIC_FOURTH_ORDER; acc_in may equal acc_out)
+ *                       RK_CLASSIC_FOURTH_ORDER).  One fma per output.  As
+ *                       for gdm_mass_solve_rk, a written vector (acc_out,
+ *                       Y) may equal a read one (acc_in, y) -- the first
+ *                       stage in place is acc_out == acc_in == y -- and
+ *                       acc_out and Y are distinct; k overlaps no output.
+ *                       Vectors that are not all 16-byte aligned take an
+ *                       entry-by-entry kernel with the same bits.
  *   gdm_eval_boundary   bc_values (device order, n_bc_points) = g(t)
  *                       (derivative 0) or dg/dt(t) (derivative 1) at the
  *                       boundary points for a built-in function:
@@ -973,7 +989,9 @@ int gdm_fastdiag_transform(gdm_op *op, int axis, int transpose, const double *sr
  *                        of gdm_add_load's fq (integrate_difference against a
  *                        function that is not built in, elasticity_01_gdm.cc:
  *                        186-198; one call per component, L2 = sqrt(sum_c
- *                        L2_c^2)).  Single rank.  Any kind.
+ *                        L2_c^2)).  On several ranks exact_q is the whole
+ *                        mesh's grid on every rank, which reads the cells
+ *                        it owns.  Any kind.
  * ---------------------------------------------------------------------- */
 int gdm_elasticity_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
 int gdm_elasticity_tables_1d(const gdm_mesh_desc *mesh, int axis, double *bands_host, double *S_host,
