@@ -1,7 +1,7 @@
 // gdm_bcfn.h -- device evaluation of the built-in boundary functions
 // (include/gdm_hip.h gdm_fn_kind) at the boundary points of one face, shared
 // by the bc evaluation kernels (gdm_rk.hip, gdm_eval_boundary) and the face
-// kernels of the inflow term (gdm_kernels.hip, gdm_apply_bc_fn), so both
+// kernels of the inflow term (gdm_face.hip, gdm_apply_bc_fn), so both
 // produce the same bits for the same point and time.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gdm_parts.h"
+
 namespace gdmk {
 
 // Kernel geometry per degree: a workgroup owns a TX x TY tile of nodes and ZC
@@ -74,37 +76,23 @@ struct CgFace {
 }  // namespace gdmk
 
 extern "C" {
-// degree-independent part (gdm_coefgrid.o, -DGDM_CG_PART=0)
+// degree-independent part (gdm_coefgrid.o, the unit of -DGDM_PART=0)
 //   reduce: partial[b] = sum over block b's samples of w kappa, bad[b] = number
 //           of samples that are not finite or not positive (ax NULL: w = 1)
 hipError_t gdmk_cg_reduce(const double *k, int64_t n, const gdmk::CgAxis *ax, double *partial, double *bad, int blocks,
                           hipStream_t st);
 hipError_t gdmk_cg_face(const gdmk::CgFace &F, const double *u, const double *kbc, double *scratch, double *dst,
                         hipStream_t st);
-#define GDMK_CG_DECLARE(P)                 \
-  hipError_t gdmk_cg_prepare_p##P(void);   \
-  hipError_t gdmk_cg_apply_p##P(const gdmk::CgArgs &a, hipStream_t st);
-GDMK_CG_DECLARE(1)
-GDMK_CG_DECLARE(3)
-GDMK_CG_DECLARE(5)
-GDMK_CG_DECLARE(7)
-GDMK_CG_DECLARE(9)
-#undef GDMK_CG_DECLARE
+// per degree (gdm_parts.h): prepare raises the kernel's dynamic LDS limit on the current device
+GDM_PARTS_DECLARE(gdmk_cg_prepare_p, void)
+GDM_PARTS_DECLARE(gdmk_cg_apply_p, const gdmk::CgArgs &a, hipStream_t st)
 }
 
 namespace gdmk {
 
-#define GDMK_CG_SWITCH(fn, ...)                      \
-  switch (p) {                                       \
-    case 1: return gdmk_cg_##fn##_p1(__VA_ARGS__);   \
-    case 3: return gdmk_cg_##fn##_p3(__VA_ARGS__);   \
-    case 5: return gdmk_cg_##fn##_p5(__VA_ARGS__);   \
-    case 7: return gdmk_cg_##fn##_p7(__VA_ARGS__);   \
-    case 9: return gdmk_cg_##fn##_p9(__VA_ARGS__);   \
-    default: return hipErrorInvalidValue;            \
-  }
-inline hipError_t cg_prepare(int p) { GDMK_CG_SWITCH(prepare) }
-inline hipError_t launch_cg(int p, const CgArgs &a, hipStream_t st) { GDMK_CG_SWITCH(apply, a, st) }
-#undef GDMK_CG_SWITCH
+inline hipError_t cg_prepare(int p) { GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_cg_prepare_p) }
+inline hipError_t launch_cg(int p, const CgArgs &a, hipStream_t st) {
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_cg_apply_p, a, st)
+}
 
 }  // namespace gdmk

@@ -2,8 +2,8 @@
 // coefficient kappa on the tensor Gauss grid (gdm_op_set_coefficient_grid;
 // DESIGN.md "Grid coefficient").
 //
-// One unit per degree, -DGDM_CG_PART=<p>, next to the unit of the
-// degree-independent kernels (-DGDM_CG_PART=0: the reduction of the set call and
+// One unit per degree, -DGDM_PART=<p>, next to the unit of the
+// degree-independent kernels (-DGDM_PART=0: the reduction of the set call and
 // the box-face part).
 //
 // Volume part: wave/stiffness.h:171-181 with JxW multiplied by kappa at the
@@ -34,11 +34,11 @@
 
 #include "gdm_coefgrid.h"
 
-#ifndef GDM_CG_PART
-#error "gdm_coefgrid.hip is compiled per degree: -DGDM_CG_PART=<p> (0: the degree-independent kernels)"
+#ifndef GDM_PART
+#error "gdm_coefgrid.hip is compiled per degree: -DGDM_PART=<p> (0: the degree-independent kernels)"
 #endif
 
-#if GDM_CG_PART == 0
+#if GDM_PART == 0
 
 namespace {
 
@@ -153,7 +153,7 @@ extern "C" hipError_t gdmk_cg_face(const gdmk::CgFace &F, const double *u, const
   return hipGetLastError();
 }
 
-#else  // GDM_CG_PART > 0
+#else  // GDM_PART > 0
 
 namespace {
 
@@ -355,21 +355,18 @@ __global__ __launch_bounds__(gdmk::cg_threads(P)) void cg_kernel(const gdmk::CgA
 
 }  // namespace
 
-#define GDM_CG_CAT_(a, b) a##b
-#define GDM_CG_CAT(a, b) GDM_CG_CAT_(a, b)
-#define GDM_CG_NAME(stem) GDM_CG_CAT(stem, GDM_CG_PART)
 
 extern "C" {
 
-hipError_t GDM_CG_NAME(gdmk_cg_prepare_p)(void) {
-  constexpr size_t lds = gdmk::cg_lds(GDM_CG_PART);
+hipError_t GDM_PART_NAME(gdmk_cg_prepare_p)(void) {
+  constexpr size_t lds = gdmk::cg_lds(GDM_PART);
   if (lds <= 64 * 1024) return hipSuccess;  // within the default limit
-  return hipFuncSetAttribute((const void *)cg_kernel<GDM_CG_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute((const void *)cg_kernel<GDM_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)lds);
 }
 
-hipError_t GDM_CG_NAME(gdmk_cg_apply_p)(const gdmk::CgArgs &a, hipStream_t st) {
-  constexpr int P = GDM_CG_PART, TX = gdmk::cg_tx(P), TY = gdmk::cg_ty(P), ZC = gdmk::cg_zc(P);
+hipError_t GDM_PART_NAME(gdmk_cg_apply_p)(const gdmk::CgArgs &a, hipStream_t st) {
+  constexpr int P = GDM_PART, TX = gdmk::cg_tx(P), TY = gdmk::cg_ty(P), ZC = gdmk::cg_zc(P);
   const int Nx = a.ax[0].N, Ny = a.ax[1].N, Nz = a.ax[2].N;
   if (Nx <= 0 || Ny <= 0 || Nz <= 0) return hipSuccess;
   const dim3 grid((Nx + TX - 1) / TX, (Ny + TY - 1) / TY, (Nz + ZC - 1) / ZC);

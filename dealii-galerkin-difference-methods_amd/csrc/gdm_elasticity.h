@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gdm_parts.h"
+
 namespace gdmk {
 
 // Kernel geometry: one workgroup of ELAS_TX * ELAS_TY threads owns an (x, y)
@@ -30,14 +32,10 @@ struct ElasArgs {
 
 }  // namespace gdmk
 
-// gdm_elasticity.hip compiles as one unit per degree (-DGDM_ELAS_PART=<p>) next
-// to the unit with the degree-independent kernels (-DGDM_ELAS_PART=0).
+// gdm_elasticity.hip compiles as one unit per degree next to the unit with the
+// degree-independent kernels (gdm_parts.h).
 extern "C" {
-hipError_t gdmk_elas_apply_p1(const gdmk::ElasArgs &a, int dim, hipStream_t st);
-hipError_t gdmk_elas_apply_p3(const gdmk::ElasArgs &a, int dim, hipStream_t st);
-hipError_t gdmk_elas_apply_p5(const gdmk::ElasArgs &a, int dim, hipStream_t st);
-hipError_t gdmk_elas_apply_p7(const gdmk::ElasArgs &a, int dim, hipStream_t st);
-hipError_t gdmk_elas_apply_p9(const gdmk::ElasArgs &a, int dim, hipStream_t st);
+GDM_PARTS_DECLARE(gdmk_elas_apply_p, const gdmk::ElasArgs &a, int dim, hipStream_t st)
 // to_reference 1: dst[v * nc + c] = src[c * n + v]; 0: the inverse.  src != dst.
 hipError_t gdmk_launch_interleave(int64_t n, int nc, int to_reference, const double *src, double *dst, hipStream_t st);
 }
@@ -45,14 +43,7 @@ hipError_t gdmk_launch_interleave(int64_t n, int nc, int to_reference, const dou
 namespace gdmk {
 
 inline hipError_t launch_elasticity(int p, int dim, const ElasArgs &a, hipStream_t st) {
-  switch (p) {
-    case 1: return gdmk_elas_apply_p1(a, dim, st);
-    case 3: return gdmk_elas_apply_p3(a, dim, st);
-    case 5: return gdmk_elas_apply_p5(a, dim, st);
-    case 7: return gdmk_elas_apply_p7(a, dim, st);
-    case 9: return gdmk_elas_apply_p9(a, dim, st);
-    default: return hipErrorInvalidValue;
-  }
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_elas_apply_p, a, dim, st)
 }
 
 }  // namespace gdmk

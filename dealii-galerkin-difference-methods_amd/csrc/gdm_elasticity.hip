@@ -4,7 +4,7 @@
 // 143-184 with the constraints of System::make_zero_boundary_constraints
 // (system.h:466-498).
 //
-// One unit per degree: -DGDM_ELAS_PART=<p>; -DGDM_ELAS_PART=0 is the unit of
+// One unit per degree: -DGDM_PART=<p>; -DGDM_PART=0 is the unit of
 // the degree-independent kernels (csrc/Makefile).
 //
 // y = (P A P + I - P) u on component-major vectors.  The block (c, e) of A is
@@ -33,13 +33,13 @@
 
 #include "gdm_elasticity.h"
 
-#ifndef GDM_ELAS_PART
-#error "gdm_elasticity.hip is compiled per degree: -DGDM_ELAS_PART=<p> (0: the shared kernels)"
+#ifndef GDM_PART
+#error "gdm_elasticity.hip is compiled per degree: -DGDM_PART=<p> (0: the shared kernels)"
 #endif
 
 namespace {
 
-#if GDM_ELAS_PART > 0
+#if GDM_PART > 0
 
 using gdmk::ELAS_TX;
 using gdmk::ELAS_TY;
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(ELAS_THREADS) void elasticity_kernel(const gdmk::El
   }
 }
 
-#else  // GDM_ELAS_PART == 0
+#else  // GDM_PART == 0
 
 __global__ __launch_bounds__(256) void interleave_kernel(int64_t n, int nc, int to_reference,
                                                          const double *__restrict__ src, double *__restrict__ dst) {
@@ -237,22 +237,20 @@ __global__ __launch_bounds__(256) void interleave_kernel(int64_t n, int nc, int 
 
 }  // namespace
 
-#define GDM_ELAS_CAT_(a, b) a##b
-#define GDM_ELAS_CAT(a, b) GDM_ELAS_CAT_(a, b)
 
 extern "C" {
 
-#if GDM_ELAS_PART > 0
+#if GDM_PART > 0
 
-hipError_t GDM_ELAS_CAT(gdmk_elas_apply_p, GDM_ELAS_PART)(const gdmk::ElasArgs &a, int dim, hipStream_t st) {
+hipError_t GDM_PART_NAME(gdmk_elas_apply_p)(const gdmk::ElasArgs &a, int dim, hipStream_t st) {
   if (a.Nx <= 0 || a.Ny <= 0 || a.Nz <= 0) return hipSuccess;
   if (dim != 2 && dim != 3) return hipErrorInvalidValue;
   const dim3 grid((a.Nx + ELAS_TX - 1) / ELAS_TX, (a.Ny + ELAS_TY - 1) / ELAS_TY, (a.Nz + ELAS_ZC - 1) / ELAS_ZC);
   if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
   if (dim == 2)
-    hipLaunchKernelGGL((elasticity_kernel<GDM_ELAS_PART, 2>), grid, dim3(ELAS_THREADS), 0, st, a);
+    hipLaunchKernelGGL((elasticity_kernel<GDM_PART, 2>), grid, dim3(ELAS_THREADS), 0, st, a);
   else
-    hipLaunchKernelGGL((elasticity_kernel<GDM_ELAS_PART, 3>), grid, dim3(ELAS_THREADS), 0, st, a);
+    hipLaunchKernelGGL((elasticity_kernel<GDM_PART, 3>), grid, dim3(ELAS_THREADS), 0, st, a);
   return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// gdm_kernels.h -- device-side argument blocks and launchers of gdm_kernels.hip.
+// gdm_kernels.h -- device-side argument blocks and launchers of gdm_stencil.hip, gdm_face.hip, gdm_mass.hip and gdm_vec.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -28,16 +28,16 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "gdm_device.h"
 #include "gdm_kernels.h"
+#include "gdm_parts.h"
+
+#ifndef GDM_PART
+#error "gdm_mass.hip is compiled per degree: -DGDM_PART=<p> (0: the two-sweep solves and the degree dispatch)"
+#endif
 
 namespace gdmk {
 
-#define GDM_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-// wave-uniform coefficient reads through the constant address space (scalar loads)
-typedef __attribute__((address_space(4))) const double cdouble;
-__device__ __forceinline__ cdouble *cptr(const double *p) { return (cdouble *)(p); }
-typedef double dpair __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) dpair ldouble2;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
@@ -907,15 +907,10 @@ hipError_t launch_mass3_rk_p(const double *src, int len, int64_t n_lines, const 
 
 }  // namespace
 
-// The single-sweep kernels of one degree take minutes to compile, so the build
-// compiles this file once per degree and entry point, side by side: a unit
-// built with -DGDM_MASS_PART=<p> holds only mass3_part<p> (the kernels of
-// gdmk_launch_mass3 at that degree), one built with -DGDM_MASS_RK_PART=<p>
-// only mass3_rk_part<p> (those of gdmk_launch_mass3_rk); the main unit, built
-// with -DGDM_MASS_SPLIT, holds everything else and calls them.  With none of
-// the macros one unit holds it all.
-#define GDM_CAT_(a, b) a##b
-#define GDM_CAT(a, b) GDM_CAT_(a, b)
+// A unit of degree p (gdm_parts.h) holds only mass3_part<p>, the kernels of
+// gdmk_launch_mass3 at that degree, or, built with -DGDM_MASS_RK as well, only
+// mass3_rk_part<p>, those of gdmk_launch_mass3_rk; unit 0 holds everything
+// else and calls them.
 #define GDM_MASS3_ARGS                                                                                          \
   int dir_kind, const double *src, double *dst, int len, int64_t stride, int64_t n_lines, int64_t A, int64_t B, \
       const double *lrow, const double *urow, const double *invd, const double *cst, int row_lo, int row_hi,    \
@@ -923,30 +918,67 @@ hipError_t launch_mass3_rk_p(const double *src, int len, int64_t n_lines, const 
 #define GDM_MASS3_RK_ARGS                                                                                     \
   const double *src, int len, int64_t n_lines, const double *lrow, const double *urow, const double *invd,    \
       const double *cst, int row_lo, int row_hi, const RkOut &rk, hipStream_t st
-#if defined(GDM_MASS_PART)
-hipError_t GDM_CAT(mass3_part, GDM_MASS_PART)(GDM_MASS3_ARGS) {
-  return launch_mass3_p<GDM_MASS_PART>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo,
-                                       row_hi, allow_segments, st);
+#if GDM_PART > 0 && defined(GDM_MASS_RK)
+hipError_t GDM_PART_NAME(mass3_rk_part)(GDM_MASS3_RK_ARGS) {
+  return launch_mass3_rk_p<GDM_PART>(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
 }
-#elif defined(GDM_MASS_RK_PART)
-hipError_t GDM_CAT(mass3_rk_part, GDM_MASS_RK_PART)(GDM_MASS3_RK_ARGS) {
-  return launch_mass3_rk_p<GDM_MASS_RK_PART>(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
+#elif GDM_PART > 0
+hipError_t GDM_PART_NAME(mass3_part)(GDM_MASS3_ARGS) {
+  return launch_mass3_p<GDM_PART>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo,
+                                  row_hi, allow_segments, st);
 }
-#elif defined(GDM_MASS_SPLIT)
-#define GDM_MASS_PART_DECL(P)                  \
-  hipError_t mass3_part##P(GDM_MASS3_ARGS); \
-  hipError_t mass3_rk_part##P(GDM_MASS3_RK_ARGS);
-GDM_MASS_PART_DECL(3) GDM_MASS_PART_DECL(5) GDM_MASS_PART_DECL(7)
-#define GDM_MASS3(P) mass3_part##P
-#define GDM_MASS3_RK(P) mass3_rk_part##P
 #else
-#define GDM_MASS3(P) launch_mass3_p<P>
-#define GDM_MASS3_RK(P) launch_mass3_rk_p<P>
+GDM_PARTS_DECLARE_IN(GDM_FOR_EACH_MASS3_DEGREE, mass3_part, GDM_MASS3_ARGS)
+GDM_PARTS_DECLARE_IN(GDM_FOR_EACH_MASS3_DEGREE, mass3_rk_part, GDM_MASS3_RK_ARGS)
 #endif
+
+// ---------------------------------------------------------------------------
+// Exact Kronecker mass inverse: banded Cholesky solves along one direction.
+// One thread per line; the position along the line is wave-uniform, so the
+// factor entries are scalar loads.  line l -> base = (l / A) * B + (l % A) * C.
+// lrow: (len + P) x (P + 1), rows >= len zero-padded.
+// ---------------------------------------------------------------------------
+template <int P>
+__global__ void __launch_bounds__(256) chol_lines_kernel(double *__restrict__ v, int len, int64_t stride,
+                                                          int64_t n_lines, int64_t A, int64_t B, int64_t C,
+                                                          const double *__restrict__ lrow,
+                                                          const double *__restrict__ inv_diag) {
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= n_lines) return;
+  double *line = v + (l / A) * B + (l % A) * C;
+  double win[P];
+#pragma unroll
+  for (int k = 0; k < P; ++k) win[k] = 0.0;
+  // forward: w_i = (r_i - sum_k L(i, i-P+k) w_{i-P+k}) / L(i,i)
+  for (int i = 0; i < len; ++i) {
+    const double *L = lrow + (size_t)i * (P + 1);
+    double s = line[(int64_t)i * stride];
+#pragma unroll
+    for (int k = 0; k < P; ++k) s = fma(-L[k], win[k], s);
+    s *= inv_diag[i];
+    line[(int64_t)i * stride] = s;
+#pragma unroll
+    for (int k = 0; k < P - 1; ++k) win[k] = win[k + 1];
+    win[P - 1] = s;
+  }
+#pragma unroll
+  for (int k = 0; k < P; ++k) win[k] = 0.0;
+  // backward: x_i = (w_i - sum_m L(i+m, i) x_{i+m}) / L(i,i)
+  for (int i = len - 1; i >= 0; --i) {
+    double s = line[(int64_t)i * stride];
+#pragma unroll
+    for (int m = 1; m <= P; ++m) s = fma(-lrow[(size_t)(i + m) * (P + 1) + (P - m)], win[m - 1], s);
+    s *= inv_diag[i];
+    line[(int64_t)i * stride] = s;
+#pragma unroll
+    for (int m = P - 1; m > 0; --m) win[m] = win[m - 1];
+    win[0] = s;
+  }
+}
 
 }  // namespace gdmk
 
-#if !defined(GDM_MASS_PART) && !defined(GDM_MASS_RK_PART)
+#if GDM_PART == 0
 extern "C" hipError_t gdmk_launch_mass3_rk(int p, const double *src, int len, int64_t n_lines, const double *lrow,
                                           const double *urow, const double *invd, const double *cst, int row_lo,
                                           int row_hi, const gdmk::RkOut &rk, hipStream_t st) {
@@ -955,12 +987,8 @@ extern "C" hipError_t gdmk_launch_mass3_rk(int p, const double *src, int len, in
   auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if (len % 2 != 0 || !al16(src) || !al16(rk.acc_in) || !al16(rk.acc_out) || (rk.Y && (!al16(rk.y) || !al16(rk.Y))))
     return hipErrorNotSupported;
-  switch (p) {
-    case 3: return GDM_MASS3_RK(3)(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
-    case 5: return GDM_MASS3_RK(5)(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
-    case 7: return GDM_MASS3_RK(7)(src, len, n_lines, lrow, urow, invd, cst, row_lo, row_hi, rk, st);
-    default: return hipErrorNotSupported;
-  }
+  GDM_PARTS_SWITCH_IN(GDM_FOR_EACH_MASS3_DEGREE, p, hipErrorNotSupported, mass3_rk_part, src, len, n_lines, lrow, urow, invd,
+                      cst, row_lo, row_hi, rk, st)
 }
 
 // v3 single-sweep line solves.  Tables: lrow [rows][p], urow [rows][p], invd
@@ -972,9 +1000,10 @@ extern "C" int gdmk_mass3_seg_waves() { return GDM_MASS_SEG_WAVES; }
 
 extern "C" int gdmk_mass3_chunk(int p) {
   switch (p) {
-    case 3: return gdmk::Geo3<3>::C;
-    case 5: return gdmk::Geo3<5>::C;
-    case 7: return gdmk::Geo3<7>::C;
+#define GDM_MASS3_CHUNK(P, ...) \
+  case P: return gdmk::Geo3<P>::C;
+    GDM_FOR_EACH_MASS3_DEGREE(GDM_MASS3_CHUNK)
+#undef GDM_MASS3_CHUNK
     default: return 0;
   }
 }
@@ -984,12 +1013,8 @@ extern "C" hipError_t gdmk_launch_mass3(int p, int dir_kind, const double *src, 
                                        int allow_segments, hipStream_t st) {
   using namespace gdmk;
   if (n_lines <= 0 || len <= 0) return hipSuccess;
-  switch (p) {
-    case 3: return GDM_MASS3(3)(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
-    case 5: return GDM_MASS3(5)(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
-    case 7: return GDM_MASS3(7)(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st);
-    default: return hipErrorInvalidValue;
-  }
+  GDM_PARTS_SWITCH_IN(GDM_FOR_EACH_MASS3_DEGREE, p, hipErrorInvalidValue, mass3_part, dir_kind, src, dst, len, stride,
+                      n_lines, A, B, lrow, urow, invd, cst, row_lo, row_hi, allow_segments, st)
 }
 
 // dir_kind 0: contiguous lines (line l at l * len, stride 1);
@@ -1002,12 +1027,29 @@ extern "C" hipError_t gdmk_launch_mass_lines(int p, int dir_kind, const double *
   using namespace gdmk;
   if (n_lines <= 0 || len <= 0) return hipSuccess;
   switch (p) {
-    case 1: return launch_mass_lines_p<1>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, inv_diag, max_wgs, st);
-    case 3: return launch_mass_lines_p<3>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, inv_diag, max_wgs, st);
-    case 5: return launch_mass_lines_p<5>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, inv_diag, max_wgs, st);
-    case 7: return launch_mass_lines_p<7>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, inv_diag, max_wgs, st);
-    case 9: return launch_mass_lines_p<9>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, inv_diag, max_wgs, st);
+#define GDM_MASS_LINES(P, ...) \
+  case P: return launch_mass_lines_p<P>(dir_kind, src, dst, len, stride, n_lines, A, B, lrow, inv_diag, max_wgs, st);
+    GDM_FOR_EACH_DEGREE(GDM_MASS_LINES)
+#undef GDM_MASS_LINES
     default: return hipErrorInvalidValue;
   }
 }
-#endif  // not a per-degree unit
+
+extern "C" hipError_t gdmk_launch_chol_lines(int p, double *v, int len, int64_t stride, int64_t n_lines, int64_t A,
+                                             int64_t B, int64_t C, const double *lrow, const double *inv_diag,
+                                             hipStream_t st) {
+  using namespace gdmk;
+  if (n_lines <= 0) return hipSuccess;
+  dim3 grid((unsigned)((n_lines + 255) / 256)), block(256);
+  switch (p) {
+#define GDM_CHOL_LINES(P, ...)                                                                                        \
+  case P:                                                                                                            \
+    hipLaunchKernelGGL(chol_lines_kernel<P>, grid, block, 0, st, v, len, stride, n_lines, A, B, C, lrow, inv_diag); \
+    break;
+    GDM_FOR_EACH_DEGREE(GDM_CHOL_LINES)
+#undef GDM_CHOL_LINES
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+#endif  // GDM_PART == 0

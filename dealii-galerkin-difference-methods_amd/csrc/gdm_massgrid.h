@@ -70,37 +70,24 @@ inline int mg_pick_zc(int p, int Nx, int Ny, int Nz, int n_cu) {
 }  // namespace gdmk
 
 extern "C" {
-// degree-independent part (gdm_massgrid.o, -DGDM_MG_PART=0):
+// degree-independent part (gdm_massgrid.o, the unit of -DGDM_PART=0):
 //   out[i] = (diag[i] / mdiag[i])^-1/2, 1 where the ratio is not positive
 hipError_t gdmk_mg_wisqrt(int64_t n, const double *diag, const double *mdiag, double *out, hipStream_t st);
-// per degree: prepare raises the kernel's dynamic LDS limit on the current device; apply is the one volume
+// per degree (gdm_parts.h): prepare raises the kernel's dynamic LDS limit on the current device; apply is the one volume
 // launch; diag writes diag(M[rho]) to a.dst (src, add and c are not read)
-#define GDMK_MG_DECLARE(P)                                              \
-  hipError_t gdmk_mg_prepare_p##P(void);                                \
-  hipError_t gdmk_mg_apply_p##P(const gdmk::MgArgs &a, hipStream_t st); \
-  hipError_t gdmk_mg_diag_p##P(const gdmk::MgArgs &a, hipStream_t st);
-GDMK_MG_DECLARE(1)
-GDMK_MG_DECLARE(3)
-GDMK_MG_DECLARE(5)
-GDMK_MG_DECLARE(7)
-GDMK_MG_DECLARE(9)
-#undef GDMK_MG_DECLARE
+GDM_PARTS_DECLARE(gdmk_mg_prepare_p, void)
+GDM_PARTS_DECLARE(gdmk_mg_apply_p, const gdmk::MgArgs &a, hipStream_t st)
+GDM_PARTS_DECLARE(gdmk_mg_diag_p, const gdmk::MgArgs &a, hipStream_t st)
 }
 
 namespace gdmk {
 
-#define GDMK_MG_SWITCH(fn, ...)                      \
-  switch (p) {                                       \
-    case 1: return gdmk_mg_##fn##_p1(__VA_ARGS__);   \
-    case 3: return gdmk_mg_##fn##_p3(__VA_ARGS__);   \
-    case 5: return gdmk_mg_##fn##_p5(__VA_ARGS__);   \
-    case 7: return gdmk_mg_##fn##_p7(__VA_ARGS__);   \
-    case 9: return gdmk_mg_##fn##_p9(__VA_ARGS__);   \
-    default: return hipErrorInvalidValue;            \
-  }
-inline hipError_t mg_prepare(int p) { GDMK_MG_SWITCH(prepare) }
-inline hipError_t launch_mg(int p, const MgArgs &a, hipStream_t st) { GDMK_MG_SWITCH(apply, a, st) }
-inline hipError_t launch_mg_diag(int p, const MgArgs &a, hipStream_t st) { GDMK_MG_SWITCH(diag, a, st) }
-#undef GDMK_MG_SWITCH
+inline hipError_t mg_prepare(int p) { GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_mg_prepare_p) }
+inline hipError_t launch_mg(int p, const MgArgs &a, hipStream_t st) {
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_mg_apply_p, a, st)
+}
+inline hipError_t launch_mg_diag(int p, const MgArgs &a, hipStream_t st) {
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_mg_diag_p, a, st)
+}
 
 }  // namespace gdmk

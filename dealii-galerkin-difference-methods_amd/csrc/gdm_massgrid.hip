@@ -1,8 +1,8 @@
 // gdm_massgrid.hip -- the mass matrix weighted by a general density rho on the
 // tensor Gauss grid (gdm_op_set_density_grid; DESIGN.md "Grid density").
 //
-// One unit per degree, -DGDM_MG_PART=<p>, next to the unit of the
-// degree-independent kernel (-DGDM_MG_PART=0: W^-1/2 of the preconditioner).
+// One unit per degree, -DGDM_PART=<p>, next to the unit of the
+// degree-independent kernel (-DGDM_PART=0: W^-1/2 of the preconditioner).
 //
 // wave/mass.h:47-249 with JxW multiplied by rho at the quadrature point, as
 // sweeps over the whole grid instead of a cell loop:
@@ -32,11 +32,11 @@
 
 #include "gdm_massgrid.h"
 
-#ifndef GDM_MG_PART
-#error "gdm_massgrid.hip is compiled per degree: -DGDM_MG_PART=<p> (0: the degree-independent kernel)"
+#ifndef GDM_PART
+#error "gdm_massgrid.hip is compiled per degree: -DGDM_PART=<p> (0: the degree-independent kernel)"
 #endif
 
-#if GDM_MG_PART == 0
+#if GDM_PART == 0
 
 namespace {
 
@@ -57,7 +57,7 @@ extern "C" hipError_t gdmk_mg_wisqrt(int64_t n, const double *diag, const double
   return hipGetLastError();
 }
 
-#else  // GDM_MG_PART > 0
+#else  // GDM_PART > 0
 
 namespace {
 
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(gdmk::MG_THREADS) void mg_kernel(const gdmk::MgArgs
 
 template <bool DIAG>
 hipError_t mg_launch(const gdmk::MgArgs &a, hipStream_t st) {
-  constexpr int P = GDM_MG_PART, TX = gdmk::mg_tx(P), TY = gdmk::mg_ty(P);
+  constexpr int P = GDM_PART, TX = gdmk::mg_tx(P), TY = gdmk::mg_ty(P);
   const int Nx = a.ax[0].N, Ny = a.ax[1].N, Nz = a.ax[2].N;
   if (Nx <= 0 || Ny <= 0 || Nz <= 0) return hipSuccess;
   if (a.zc < 1 || a.zc > gdmk::mg_zc(P)) return hipErrorInvalidValue;
@@ -259,25 +259,22 @@ hipError_t mg_launch(const gdmk::MgArgs &a, hipStream_t st) {
 
 }  // namespace
 
-#define GDM_MG_CAT_(a, b) a##b
-#define GDM_MG_CAT(a, b) GDM_MG_CAT_(a, b)
-#define GDM_MG_NAME(stem) GDM_MG_CAT(stem, GDM_MG_PART)
 
 extern "C" {
 
-hipError_t GDM_MG_NAME(gdmk_mg_prepare_p)(void) {
-  constexpr size_t lds = gdmk::mg_lds(GDM_MG_PART);
+hipError_t GDM_PART_NAME(gdmk_mg_prepare_p)(void) {
+  constexpr size_t lds = gdmk::mg_lds(GDM_PART);
   if (lds <= 64 * 1024) return hipSuccess;  // within the default limit
-  hipError_t e = hipFuncSetAttribute((const void *)mg_kernel<GDM_MG_PART, false>,
+  hipError_t e = hipFuncSetAttribute((const void *)mg_kernel<GDM_PART, false>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void *)mg_kernel<GDM_MG_PART, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute((const void *)mg_kernel<GDM_PART, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)lds);
 }
 
-hipError_t GDM_MG_NAME(gdmk_mg_apply_p)(const gdmk::MgArgs &a, hipStream_t st) { return mg_launch<false>(a, st); }
+hipError_t GDM_PART_NAME(gdmk_mg_apply_p)(const gdmk::MgArgs &a, hipStream_t st) { return mg_launch<false>(a, st); }
 
-hipError_t GDM_MG_NAME(gdmk_mg_diag_p)(const gdmk::MgArgs &a, hipStream_t st) { return mg_launch<true>(a, st); }
+hipError_t GDM_PART_NAME(gdmk_mg_diag_p)(const gdmk::MgArgs &a, hipStream_t st) { return mg_launch<true>(a, st); }
 
 }  // extern "C"
 

@@ -1,5 +1,5 @@
-// gdm_kernels.hip -- hand-written CDNA4 (gfx950) kernels of the GDM operator
-// engine.  See DESIGN.md for the derivation; in short, on an uncut uniform
+// gdm_stencil.hip -- the fused Kronecker stencil of the GDM operator engine
+// (hand-written CDNA4, gfx950), v7 for small meshes and v8 for the rest.  See DESIGN.md for the derivation; in short, on an uncut uniform
 // Cartesian mesh every hot-path operator of the reference is a sum of
 // Kronecker products of 1D band matrices of half-bandwidth p:
 //
@@ -23,7 +23,14 @@
 #include <cstdlib>
 
 #include "gdm_coeffs.h"
+#include "gdm_device.h"
+#include "gdm_face.h"
 #include "gdm_kernels.h"
+#include "gdm_parts.h"
+
+#ifndef GDM_PART
+#error "gdm_stencil.hip is compiled per degree: -DGDM_PART=<p> (0: the degree dispatch and the geometry queries)"
+#endif
 
 #ifndef GDM_R5
 #define GDM_R5 4
@@ -58,17 +65,6 @@
 #endif
 
 namespace gdmk {
-
-
-
-#define GDM_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define GDM_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-// Coefficient tables are read-only for the whole launch and indexed by
-// wave-uniform positions: read them through the constant address space so
-// they become scalar (s_load) loads instead of vector loads.
-typedef __attribute__((address_space(4))) const double cdouble;
-__device__ __forceinline__ cdouble *cptr(const double *p) { return (cdouble *)(p); }
 
 // ===========================================================================
 // Fused Kronecker stencil, v7: producer / consumer waves.
@@ -135,10 +131,6 @@ struct Dma7 {
   }
 };
 
-typedef __attribute__((address_space(3))) double ldouble;
-typedef __attribute__((address_space(3))) unsigned int lu32;
-typedef double dpair __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) dpair ldouble2;
 typedef __attribute__((address_space(3))) const double lcdouble;
 typedef __attribute__((address_space(3))) const dpair lcdouble2;
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
@@ -580,217 +572,6 @@ __global__ void __launch_bounds__(64 * (NP + NC), (64 * (NP + NC)) / 256) stenci
     producer7<P, R, NC, NP, BK, CH>(a, t);
   else
     consumer7<P, R, NC, NP, BK>(a, t);
-}
-
-// ---------------------------------------------------------------------------
-// Inflow boundary-data term (advection/stiffness.h:473-532 with a.n < 0):
-//   rhs(node) += |a.n| sum_{q on face} u+_q phi_node(x_q) JxW_q
-// factorised over the two tangential directions of the face:
-//   step 1: T[q1][i0] = sum_m U[q1][qs0(i0) + m] w0[i0][m]
-//   step 2: dst(i0, i1) += scale * sum_m w1[i1][m] T[qs1(i1) + m][i0]
-// Step 1 stages ROWS rows of U (the q-range of FACE_CHUNK consecutive nodes)
-// in LDS with coalesced loads; each lane then owns one node and reads its
-// weights node-minor (w0T), so every global access is a contiguous wave row.
-// ---------------------------------------------------------------------------
-// boundary values U(i0, i1) of the face ([Q1][Q0] array).  (Evaluating the
-// stage values of a built-in function here instead, per point, measured 2-3x
-// slower than reading them: each lane's six consecutive points make every
-// table read touch 64 cache lines; gdm_apply_bc_fn fills the array first.)
-struct BcArr {
-  const double *__restrict__ U;
-  int Q0;
-  __device__ __forceinline__ double operator()(int i0, int i1) const { return U[(int64_t)i1 * Q0 + i0]; }
-};
-
-
-template <int ROWS, class Src>
-__global__ void __launch_bounds__(FACE_CHUNK) face_step1_kernel(const Src U, int Q0, int Q1,
-                                                                 int i0_begin, int n0,
-                                                                 const int *__restrict__ qs0,
-                                                                 const double *__restrict__ w0T, int wmax0,
-                                                                 int ldw0, int qmax, double *__restrict__ T) {
-  extern __shared__ double sh[];  // [ROWS][qmax]
-  const int c0 = blockIdx.x * FACE_CHUNK;
-  const int q1b = blockIdx.y * ROWS;
-  const int nc = min(FACE_CHUNK, n0 - c0);
-  const int ia = i0_begin + c0;
-  const int qa = qs0[ia];
-  const int nq = min(Q0, qs0[ia + nc - 1] + wmax0) - qa;  // <= qmax (host-checked)
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    if (q1b + r < Q1) {
-      for (int e = threadIdx.x; e < nq; e += FACE_CHUNK) sh[r * qmax + e] = U(qa + e, q1b + r);
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x >= nc) return;
-  const int i0 = ia + threadIdx.x;
-  const int b = qs0[i0] - qa;
-  const int mend = min(wmax0, nq - b);  // weights past the node's own count are 0
-  double s[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) s[r] = 0.0;
-  for (int m = 0; m < mend; ++m) {
-    const double w = w0T[(int64_t)m * ldw0 + i0];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) s[r] = fma(w, sh[r * qmax + b + m], s[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-    if (q1b + r < Q1) T[(int64_t)(q1b + r) * n0 + c0 + threadIdx.x] = s[r];
-}
-
-// Step 1 in cell form: for one row q1 of the face, every local cell c reduces
-// its p + 1 contiguous boundary values with its category's (p+1) x (p+1) table
-// (S_c[l] = sum_q Phi[cat(c)][l][q] U[q1][c (p+1) + q], one contiguous read per
-// cell, no per-node weight rows), then every owned node gathers the S_c of the
-// cells whose DoF boxes contain it (system.h:195-246 box offsets).
-__device__ __forceinline__ int face_category(int c, int p, int n) {
-  const int half = p / 2;
-  return c < half ? c : (c < n - half ? half : p + c - n);
-}
-__device__ __forceinline__ int face_box_offset(int c, int p, int n) {
-  const int half = p / 2;
-  return c < half ? 0 : min(n, c + half + 1) - p;
-}
-
-template <int P, class Src>
-__device__ __forceinline__ void face_cell_step1_body(const Src &U, int Q0, int Q1, int rpb, int i0_begin, int n0,
-                                                     const int *__restrict__ crange, const double *__restrict__ phi,
-                                                     int ncell_total, int cell_begin, double *__restrict__ T,
-                                                     int block) {
-  constexpr int N1 = P + 1;
-  extern __shared__ double sh[];  // [P][N1][N1] Phi, then [ncells][N1] S
-  double *sphi = sh, *S = sh + P * N1 * N1;
-  const int ncells = Q0 / N1;
-  for (int e = threadIdx.x; e < P * N1 * N1; e += blockDim.x) sphi[e] = phi[e];
-  const int r0 = block * rpb, r1 = min(Q1, r0 + rpb);
-  for (int row = r0; row < r1; ++row) {
-    __syncthreads();  // Phi ready / previous row's gather done
-    for (int c = threadIdx.x; c < ncells; c += blockDim.x) {
-      const int cat = face_category(cell_begin + c, P, ncell_total);
-      double v[N1];
-#pragma unroll
-      for (int q = 0; q < N1; ++q) v[q] = U(c * N1 + q, row);
-      const double *ph = sphi + cat * N1 * N1;
-#pragma unroll
-      for (int l = 0; l < N1; ++l) {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < N1; ++q) s = fma(ph[l * N1 + q], v[q], s);
-        S[c * N1 + l] = s;
-      }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < n0; t += blockDim.x) {
-      const int i0 = i0_begin + t;
-      const int cf = crange[2 * i0], cl = crange[2 * i0 + 1];
-      double acc = 0.0;
-      for (int c = cf; c <= cl; ++c) acc += S[c * N1 + (i0 - face_box_offset(cell_begin + c, P, ncell_total))];
-      T[(int64_t)row * n0 + t] = acc;
-    }
-  }
-}
-
-// Step 1 of the rows [block rpb, block rpb + rpb) at once, all threads of the
-// workgroup (the stencil's tail): the rows (contiguous in U) are staged in LDS
-// with coalesced 16-B loads, all of them in flight together; each (row, cell)
-// reduction then reads its N1 values from LDS and writes its N1 results over
-// them (the same positions: in place, no barrier); one barrier; every
-// (row, node) gather.  The same sums in the same order as
-// face_cell_step1_body.  LDS: Phi, then [rpb][Q0] (U rows, then S).
-template <int P>
-__device__ __forceinline__ void face_cell_step1_rows(const BcArr &U, int Q0, int Q1, int rpb, int i0_begin, int n0,
-                                                     const int *__restrict__ crange, const double *__restrict__ phi,
-                                                     int ncell_total, int cell_begin, double *__restrict__ T,
-                                                     int block) {
-  constexpr int N1 = P + 1, MAXLD = 8;
-  extern __shared__ double sh[];
-  double *sphi = sh, *S = sh + ((P * N1 * N1 + 1) & ~1);  // 16-B aligned rows
-  const int ncells = Q0 / N1;
-  for (int e = threadIdx.x; e < P * N1 * N1; e += blockDim.x) sphi[e] = phi[e];
-  const int r0 = block * rpb, nr = min(Q1, r0 + rpb) - r0;
-  // stage rows r0 .. r0 + nr - 1 (nr * Q0 contiguous doubles of U)
-  const double *src = U.U + (int64_t)r0 * Q0;
-  const int n = nr * Q0;
-  if ((((uintptr_t)src) & 15) == 0 && (n & 1) == 0) {
-    const dpair *s2 = (const dpair *)src;
-    ldouble2 *d2 = (ldouble2 *)S;
-    for (int eb = 0; eb < n / 2; eb += MAXLD * (int)blockDim.x) {
-      dpair v[MAXLD];
-#pragma unroll
-      for (int k = 0; k < MAXLD; ++k) {
-        const int e = eb + k * (int)blockDim.x + (int)threadIdx.x;
-        if (e < n / 2) v[k] = __builtin_nontemporal_load(s2 + e);
-      }
-#pragma unroll
-      for (int k = 0; k < MAXLD; ++k) {
-        const int e = eb + k * (int)blockDim.x + (int)threadIdx.x;
-        if (e < n / 2) d2[e] = v[k];
-      }
-    }
-  } else {
-    for (int e = threadIdx.x; e < n; e += blockDim.x) S[e] = src[e];
-  }
-  __syncthreads();  // Phi and the rows staged
-  for (int e = threadIdx.x; e < nr * ncells; e += blockDim.x) {
-    const int r = e / ncells, c = e - r * ncells;
-    double *Sc = S + (int64_t)r * Q0 + c * N1;
-    double v[N1];
-#pragma unroll
-    for (int q = 0; q < N1; ++q) v[q] = Sc[q];
-    const double *ph = sphi + face_category(cell_begin + c, P, ncell_total) * N1 * N1;
-#pragma unroll
-    for (int l = 0; l < N1; ++l) {
-      double acc = 0.0;
-#pragma unroll
-      for (int q = 0; q < N1; ++q) acc = fma(ph[l * N1 + q], v[q], acc);
-      Sc[l] = acc;
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < nr * n0; e += blockDim.x) {
-    const int r = e / n0, t = e - r * n0;
-    const int i0 = i0_begin + t;
-    const int cf = crange[2 * i0], cl = crange[2 * i0 + 1];
-    const double *Sr = S + (int64_t)r * Q0;
-    double acc = 0.0;
-    for (int c = cf; c <= cl; ++c) acc += Sr[c * N1 + (i0 - face_box_offset(cell_begin + c, P, ncell_total))];
-    T[(int64_t)(r0 + r) * n0 + t] = acc;
-  }
-}
-
-template <int P, class Src>
-__global__ void __launch_bounds__(512) face_cell_step1_kernel(const Src U, int Q0, int Q1, int rpb,
-                                                               int i0_begin, int n0, const int *__restrict__ crange,
-                                                               const double *__restrict__ phi, int ncell_total,
-                                                               int cell_begin, double *__restrict__ T) {
-  face_cell_step1_body<P>(U, Q0, Q1, rpb, i0_begin, n0, crange, phi, ncell_total, cell_begin, T, blockIdx.x);
-}
-
-// every inflow face's step 1 (cell form) in one launch, face = blockIdx.y:
-// the faces are independent (own T), so their rows share the GPU instead of
-// running one face after the other (gdmk_launch_faces_step1)
-template <class Src>
-struct Step1Face {
-  Src U;
-  int Q0, Q1, i0_begin, n0;
-  const int *crange;
-  const double *phi;
-  int ncell_total, cell_begin;
-  double *T;
-};
-template <class Src>
-struct Step1Set {
-  Step1Face<Src> f[BcStage::kMaxFaces];
-  int rpb;
-};
-template <int P, class Src>
-__global__ void __launch_bounds__(512) face_cell_step1_multi_kernel(const Step1Set<Src> set) {
-  const Step1Face<Src> &F = set.f[blockIdx.y];
-  if ((int)blockIdx.x * set.rpb >= F.Q1) return;
-  face_cell_step1_body<P>(F.U, F.Q0, F.Q1, set.rpb, F.i0_begin, F.n0, F.crange, F.phi, F.ncell_total, F.cell_begin,
-                          F.T, blockIdx.x);
 }
 
 // ===========================================================================
@@ -1619,282 +1400,6 @@ __global__ void __launch_bounds__(64 * (NP + NC), ((NP + NC) * Geom8<P, R, NC, N
 }
 
 // ---------------------------------------------------------------------------
-// Exact Kronecker mass inverse: banded Cholesky solves along one direction.
-// One thread per line; the position along the line is wave-uniform, so the
-// factor entries are scalar loads.  line l -> base = (l / A) * B + (l % A) * C.
-// lrow: (len + P) x (P + 1), rows >= len zero-padded.
-// ---------------------------------------------------------------------------
-template <int P>
-__global__ void __launch_bounds__(256) chol_lines_kernel(double *__restrict__ v, int len, int64_t stride,
-                                                          int64_t n_lines, int64_t A, int64_t B, int64_t C,
-                                                          const double *__restrict__ lrow,
-                                                          const double *__restrict__ inv_diag) {
-  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= n_lines) return;
-  double *line = v + (l / A) * B + (l % A) * C;
-  double win[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) win[k] = 0.0;
-  // forward: w_i = (r_i - sum_k L(i, i-P+k) w_{i-P+k}) / L(i,i)
-  for (int i = 0; i < len; ++i) {
-    const double *L = lrow + (size_t)i * (P + 1);
-    double s = line[(int64_t)i * stride];
-#pragma unroll
-    for (int k = 0; k < P; ++k) s = fma(-L[k], win[k], s);
-    s *= inv_diag[i];
-    line[(int64_t)i * stride] = s;
-#pragma unroll
-    for (int k = 0; k < P - 1; ++k) win[k] = win[k + 1];
-    win[P - 1] = s;
-  }
-#pragma unroll
-  for (int k = 0; k < P; ++k) win[k] = 0.0;
-  // backward: x_i = (w_i - sum_m L(i+m, i) x_{i+m}) / L(i,i)
-  for (int i = len - 1; i >= 0; --i) {
-    double s = line[(int64_t)i * stride];
-#pragma unroll
-    for (int m = 1; m <= P; ++m) s = fma(-lrow[(size_t)(i + m) * (P + 1) + (P - m)], win[m - 1], s);
-    s *= inv_diag[i];
-    line[(int64_t)i * stride] = s;
-#pragma unroll
-    for (int m = P - 1; m > 0; --m) win[m] = win[m - 1];
-    win[0] = s;
-  }
-}
-
-// scale sum_m w1[i1][m] T[q + m][t], the product rounded on its own: the
-// compiler may not fuse it into the later add (one FMA would round
-// differently from the face-by-face path's dst + G)
-__device__ __forceinline__ double face_step2_value(const double *__restrict__ T, int n0, int t, int i1,
-                                                   const int *__restrict__ qs1, const int *__restrict__ qc1,
-                                                   const double *__restrict__ w1, int wmax1, double scale) {
-  const double *w = w1 + (int64_t)i1 * wmax1;
-  const int n = qc1[i1], q = qs1[i1];
-  const double *Tc = T + (int64_t)q * n0 + t;
-  double s = 0.0;
-  int m = 0;
-  // groups of 6 loads in flight, the FMAs in increasing m (the order of the
-  // one-at-a-time loop: same bits)
-  for (; m + 6 <= n; m += 6) {
-    double tv[6];
-#pragma unroll
-    for (int u = 0; u < 6; ++u) tv[u] = Tc[(int64_t)(m + u) * n0];
-#pragma unroll
-    for (int u = 0; u < 6; ++u) s = fma(w[m + u], tv[u], s);
-  }
-  for (; m < n; ++m) s = fma(w[m], Tc[(int64_t)m * n0], s);
-  double v;
-  {
-#pragma clang fp contract(off)
-    v = scale * s;
-  }
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
-#ifndef GDM_STENCIL_PART
-// dst node (t, i1) += scale sum_m w1[i1][m] T[q + m][t]: one face (face by face, in face order)
-__global__ void __launch_bounds__(256) face_step2_kernel(const double *__restrict__ T, int n0, int i1_begin,
-                                                          int i1_end, const int *__restrict__ qs1,
-                                                          const int *__restrict__ qc1,
-                                                          const double *__restrict__ w1, int wmax1,
-                                                          double *__restrict__ dst, int64_t base,
-                                                          int64_t stride0, int64_t stride1, double scale) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int i1 = i1_begin + (int)blockIdx.y;
-  if (t >= n0 || i1 >= i1_end) return;
-  const double v = face_step2_value(T, n0, t, i1, qs1, qc1, w1, wmax1, scale);
-  double *d = dst + base + (int64_t)t * stride0 + (int64_t)(i1 - i1_begin) * stride1;
-  *d = *d + v;
-}
-#endif  // !GDM_STENCIL_PART
-
-// step-2 data of one face for face_step2_add_kernel
-struct Step2Face {
-  const double *T;
-  int n0, i1_begin, i1_end;
-  const int *qs1, *qc1;
-  const double *w1;
-  int wmax1;
-  double scale;
-};
-__device__ __forceinline__ bool face_add_member(const FaceAddFace &g, const int c[3]) {
-  return c[g.d] == g.plane && (g.a0 < 0 || (c[g.a0] >= g.b0 && c[g.a0] < g.e0)) &&
-         (g.a1 < 0 || (c[g.a1] >= g.b1 && c[g.a1] < g.e1));
-}
-// step 2 of every inflow face fused with the ordered adds (one launch, face =
-// blockIdx.z): a node is handled by the thread of the first face containing
-// it, which adds its own face's G = scale sum_m w1 T and then every later
-// containing face's G, in face order -- the sums (and roundings) of the
-// per-face step-2 launches, without the G buffers and the separate add launch
-struct Step2AddSet {
-  Step2Face f[BcStage::kMaxFaces];
-  FaceAddFace g[BcStage::kMaxFaces];
-  int n;
-  int64_t N0, N1, own_off;
-};
-// One thread per node column t and R1 consecutive i1 rows: the rows' T
-// windows overlap (consecutive nodes shift by one cell), so the thread walks
-// the union of their q ranges once and feeds each row's sum in increasing m
-// -- the same FMA sequence per node as face_step2_value, with ~R1 / 4 of its
-// T loads.  Weights and q ranges are wave-uniform (scalar loads).
-template <int R1>
-__global__ void __launch_bounds__(64) face_step2_add_kernel(const Step2AddSet set, double *__restrict__ dst) {
-  const int f = blockIdx.z;
-  const Step2Face &F = set.f[f];
-  const FaceAddFace &A = set.g[f];
-  const int r0 = blockIdx.y * R1, nr = min(R1, F.i1_end - F.i1_begin - r0);
-  if (nr <= 0) return;
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  const bool on = t < F.n0;
-  const int tt = on ? t : F.n0 - 1;  // idle lanes repeat a valid column (no divergence in the q walk)
-  const int i1a = F.i1_begin + r0;
-  int qlo = F.qs1[i1a], qhi = qlo;
-#pragma unroll
-  for (int j = 0; j < R1; ++j)
-    if (j < nr) {
-      qlo = min(qlo, F.qs1[i1a + j]);
-      qhi = max(qhi, F.qs1[i1a + j] + F.qc1[i1a + j]);
-    }
-  double sum[R1];
-  int qs[R1], qe[R1];
-  const double *wr[R1];
-#pragma unroll
-  for (int j = 0; j < R1; ++j) {
-    sum[j] = 0.0;
-    qs[j] = j < nr ? F.qs1[i1a + j] : 0;
-    qe[j] = j < nr ? qs[j] + F.qc1[i1a + j] : 0;
-    wr[j] = F.w1 + (int64_t)(i1a + j) * F.wmax1 - qs[j];  // wr[j][q] = w1[i1][q - qs]
-  }
-  const double *Tc = F.T + tt;
-  int q = qlo;
-  for (; q + 6 <= qhi; q += 6) {
-    double tv[6];
-#pragma unroll
-    for (int u = 0; u < 6; ++u) tv[u] = Tc[(int64_t)(q + u) * F.n0];
-#pragma unroll
-    for (int u = 0; u < 6; ++u)
-#pragma unroll
-      for (int j = 0; j < R1; ++j)
-        if (q + u >= qs[j] && q + u < qe[j]) sum[j] = fma(wr[j][q + u], tv[u], sum[j]);
-  }
-  for (; q < qhi; ++q) {
-    const double tv = Tc[(int64_t)q * F.n0];
-#pragma unroll
-    for (int j = 0; j < R1; ++j)
-      if (q >= qs[j] && q < qe[j]) sum[j] = fma(wr[j][q], tv, sum[j]);
-  }
-  if (!on) return;
-#pragma unroll
-  for (int j = 0; j < R1; ++j) {
-    if (j >= nr) break;
-    const int r = r0 + j;
-    const int64_t o = A.base + (int64_t)t * A.stride0 + (int64_t)r * A.stride1;
-    const int64_t gi = o + set.own_off;
-    const int c[3] = {(int)(gi % set.N0), (int)((gi / set.N0) % set.N1), (int)(gi / (set.N0 * set.N1))};
-    bool mine = true;
-    for (int g = 0; g < f; ++g)
-      if (face_add_member(set.g[g], c)) mine = false;
-    if (!mine) continue;  // the node's first face adds every face's term
-    double gv;
-    {
-#pragma clang fp contract(off)
-      gv = F.scale * sum[j];
-    }
-    asm volatile("" : "+v"(gv));
-    double v = dst[o];
-    v = v + gv;
-    for (int g = f + 1; g < set.n; ++g) {
-      const FaceAddFace &H = set.g[g];
-      if (!face_add_member(H, c)) continue;
-      const Step2Face &S = set.f[g];
-      const int u0 = H.a0 < 0 ? 0 : c[H.a0] - H.b0, u1 = H.a1 < 0 ? 0 : c[H.a1] - H.b1;
-      v = v + face_step2_value(S.T, S.n0, u0, S.i1_begin + u1, S.qs1, S.qc1, S.w1, S.wmax1, S.scale);
-    }
-    dst[o] = v;
-  }
-}
-
-#ifndef GDM_STENCIL_PART
-// ---------------------------------------------------------------------------
-// BLAS-1
-// ---------------------------------------------------------------------------
-// y = a x + b y (gdm_vec_axpby).  MODE bit 0: a != 0, x is read; bit 1:
-// b != 0, y is read -- an operand with a zero factor is not loaded, so what
-// it holds (uninitialised memory, NaN, Inf) cannot reach the result.  The host
-// picks MODE from the scalars.  x may equal y (every entry is loaded before it
-// is stored, by the lane that stores it): no __restrict__.
-template <int MODE>
-__device__ __forceinline__ double axpby_value(double a, double x, double b, double y) {
-  if (MODE == 3) return fma(a, x, b * y);
-  if (MODE == 1) return a * x;
-  if (MODE == 2) return b * y;
-  return 0.0;
-}
-
-// pairs (double2); host-checked: x and y 16-B aligned.  The odd tail element,
-// if any, is done by the first lane.
-template <int MODE>
-__global__ void __launch_bounds__(256) axpby2_kernel(int64_t n, double a, const double *x, double b, double *y) {
-  const int64_t n2 = n / 2;
-  const double2 *x2 = reinterpret_cast<const double2 *>(x);
-  double2 *y2 = reinterpret_cast<double2 *>(y);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
-    double2 xv = {0.0, 0.0}, yv = {0.0, 0.0};
-    if (MODE & 1) xv = x2[i];
-    if (MODE & 2) yv = y2[i];
-    yv.x = axpby_value<MODE>(a, xv.x, b, yv.x);
-    yv.y = axpby_value<MODE>(a, xv.y, b, yv.y);
-    y2[i] = yv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1))
-    y[n - 1] = axpby_value<MODE>(a, (MODE & 1) ? x[n - 1] : 0.0, b, (MODE & 2) ? y[n - 1] : 0.0);
-}
-
-// scalar form for vectors that are not 16-B aligned
-template <int MODE>
-__global__ void __launch_bounds__(256) axpby_kernel(int64_t n, double a, const double *x, double b, double *y) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    y[i] = axpby_value<MODE>(a, (MODE & 1) ? x[i] : 0.0, b, (MODE & 2) ? y[i] : 0.0);
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-__global__ void __launch_bounds__(256) dot_partial_kernel(int64_t n, const double *__restrict__ x,
-                                                           const double *__restrict__ y,
-                                                           double *__restrict__ partial) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    s = fma(x[i], y[i], s);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void __launch_bounds__(256) dot_final_kernel(int n, const double *__restrict__ partial,
-                                                         double *__restrict__ out) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += partial[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void __launch_bounds__(256) zero_kernel(int64_t n, double *__restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    y[i] = 0.0;
-}
-#endif  // !GDM_STENCIL_PART
-
-// ---------------------------------------------------------------------------
 // host-side launchers (called from gdm_capi.cpp)
 // ---------------------------------------------------------------------------
 template <int P, int R, int NC, int NP, int BK, int CH>
@@ -2002,297 +1507,74 @@ static hipError_t launch8_p(int bk, const StencilArgs &a, const TailReq &tail, h
   }
 }
 
-// The stencil kernels of one degree take minutes to compile, so the build
-// compiles this file once per degree, side by side: a unit built with
-// -DGDM_STENCIL_PART=<p> holds only launch8_part<p> / launch7_part<p> (and the
-// kernels they instantiate), the main unit, built with -DGDM_STENCIL_SPLIT,
-// everything else and calls them.  With neither macro one unit holds it all.
-#define GDM_L8_1 launch8_p<1, 4, 8, 8, 3>
-#define GDM_L8_3 launch8_p<3, 4, 8, 8, 3>
-#define GDM_L8_5 launch8_p<5, GDM_R5, GDM_NC5, GDM_NP5, GDM_PF5>
-#define GDM_L8_7 launch8_p<7, GDM_R7, GDM_NC7, GDM_NP7, GDM_PF7>
-#define GDM_L8_9 launch8_p<9, 2, 8, 8, 3>
-#define GDM_L7_1 launch7_p<1, 4, 8, 8>
-#define GDM_L7_3 launch7_p<3, 4, 8, 8>
-#define GDM_L7_5 launch7_p<5, 4, 8, 8>
-#define GDM_L7_7 launch7_p<7, 2, 8, 8>
-#define GDM_L7_9 launch7_p<9, 2, 8, 8>
-#define GDM_CAT_(a, b) a##b
-#define GDM_CAT(a, b) GDM_CAT_(a, b)
-#if defined(GDM_STENCIL_PART)
-hipError_t GDM_CAT(launch8_part, GDM_STENCIL_PART)(int bk, const StencilArgs &a, const TailReq &tail, hipStream_t st) {
-  return GDM_CAT(GDM_L8_, GDM_STENCIL_PART)(bk, a, tail, st);
+// The tile of each degree, <P, R, NC, NP>: R output rows per consumer wave, NC
+// consumer and NP producer waves -> tile 64 x (R NC); v8 also the consumers'
+// prefetch depth PF.  Written here once: the launches and the geometry queries
+// both read these.
+#define GDM_TILE8_1 1, 4, 8, 8
+#define GDM_TILE8_3 3, 4, 8, 8
+#define GDM_TILE8_5 5, GDM_R5, GDM_NC5, GDM_NP5
+#define GDM_TILE8_7 7, GDM_R7, GDM_NC7, GDM_NP7
+#define GDM_TILE8_9 9, 2, 8, 8
+#define GDM_PF8_1 3
+#define GDM_PF8_3 3
+#define GDM_PF8_5 GDM_PF5
+#define GDM_PF8_7 GDM_PF7
+#define GDM_PF8_9 3
+#define GDM_TILE7_1 1, 4, 8, 8
+#define GDM_TILE7_3 3, 4, 8, 8
+#define GDM_TILE7_5 5, 4, 8, 8
+#define GDM_TILE7_7 7, 2, 8, 8
+#define GDM_TILE7_9 9, 2, 8, 8
+
+// A unit of degree p (gdm_parts.h) holds only launch8_part<p> / launch7_part<p>
+// and the kernels they instantiate; unit 0 dispatches to them by degree.
+#if GDM_PART > 0
+hipError_t GDM_PART_NAME(launch8_part)(int bk, const StencilArgs &a, const TailReq &tail, hipStream_t st) {
+  return launch8_p<GDM_PART_NAME(GDM_TILE8_), GDM_PART_NAME(GDM_PF8_)>(bk, a, tail, st);
 }
-hipError_t GDM_CAT(launch7_part, GDM_STENCIL_PART)(int bk, const StencilArgs &a, hipStream_t st) {
-  return GDM_CAT(GDM_L7_, GDM_STENCIL_PART)(bk, a, st);
+hipError_t GDM_PART_NAME(launch7_part)(int bk, const StencilArgs &a, hipStream_t st) {
+  return launch7_p<GDM_PART_NAME(GDM_TILE7_)>(bk, a, st);
 }
-#elif defined(GDM_STENCIL_SPLIT)
-#define GDM_PART_DECL(P)                                                                        \
-  hipError_t launch8_part##P(int bk, const StencilArgs &a, const TailReq &tail, hipStream_t st); \
-  hipError_t launch7_part##P(int bk, const StencilArgs &a, hipStream_t st);
-GDM_PART_DECL(1) GDM_PART_DECL(3) GDM_PART_DECL(5) GDM_PART_DECL(7) GDM_PART_DECL(9)
-#define GDM_LAUNCH8(P) launch8_part##P
-#define GDM_LAUNCH7(P) launch7_part##P
 #else
-#define GDM_LAUNCH8(P) GDM_L8_##P
-#define GDM_LAUNCH7(P) GDM_L7_##P
+GDM_PARTS_DECLARE(launch8_part, int bk, const StencilArgs &a, const TailReq &tail, hipStream_t st)
+GDM_PARTS_DECLARE(launch7_part, int bk, const StencilArgs &a, hipStream_t st)
 #endif
 
 }  // namespace gdmk
 
-#ifndef GDM_STENCIL_PART
+#if GDM_PART == 0
 extern "C" hipError_t gdmk_launch_stencil8(int p, int bk, const gdmk::StencilArgs &a, const gdmk::FaceArgs *tail_faces,
                                            int n_tail, unsigned long long *counter, bool *tail_ran,
                                            hipStream_t st) {
   using namespace gdmk;
   *tail_ran = false;
   const TailReq tail{tail_faces, n_tail, counter, tail_ran};
-  hipError_t e = hipErrorInvalidValue;
-  switch (p) {
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 1
-    case 1: e = GDM_LAUNCH8(1)(bk, a, tail, st); break;
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 3
-    case 3: e = GDM_LAUNCH8(3)(bk, a, tail, st); break;
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 5
-    case 5: e = GDM_LAUNCH8(5)(bk, a, tail, st); break;
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 7
-    case 7: e = GDM_LAUNCH8(7)(bk, a, tail, st); break;
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 9
-    case 9: e = GDM_LAUNCH8(9)(bk, a, tail, st); break;
-#endif
-    default: break;
-  }
-  return e;
-}
-
-// <P, R, NC, NP>: R output rows per consumer wave, NC consumer and NP producer
-// waves -> tile 64 x (R NC)
-extern "C" int gdmk_stencil_tile_rows(int p) {
-  using namespace gdmk;
-  return p < 5 ? 32 : (p == 5 ? Geom8<5, GDM_R5, GDM_NC5, GDM_NP5, 1>::TY : (p == 7 ? Geom8<7, GDM_R7, GDM_NC7, GDM_NP7, 1>::TY : 16));
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, launch8_part, bk, a, tail, st)
 }
 
 extern "C" void gdmk_stencil8_geom(int p, int *tile_rows, int *wgs_per_cu) {
   using namespace gdmk;
   switch (p) {
-    case 5:
-      *tile_rows = Geom8<5, GDM_R5, GDM_NC5, GDM_NP5, 1>::TY;
-      *wgs_per_cu = Geom8<5, GDM_R5, GDM_NC5, GDM_NP5, 1>::WGS;
-      return;
-    case 7:
-      *tile_rows = Geom8<7, GDM_R7, GDM_NC7, GDM_NP7, 1>::TY;
-      *wgs_per_cu = Geom8<7, GDM_R7, GDM_NC7, GDM_NP7, 1>::WGS;
-      return;
-    case 9: *tile_rows = 16; *wgs_per_cu = 1; return;
+#define GDM_GEOM8(P, ...)                        \
+  case P:                                        \
+    *tile_rows = Geom8<GDM_TILE8_##P, 1>::TY;    \
+    *wgs_per_cu = Geom8<GDM_TILE8_##P, 1>::WGS;  \
+    return;
+    GDM_FOR_EACH_DEGREE(GDM_GEOM8)
+#undef GDM_GEOM8
     default: *tile_rows = 32; *wgs_per_cu = 1; return;
   }
 }
 
+extern "C" int gdmk_stencil_tile_rows(int p) {
+  int tile_rows, wgs_per_cu;
+  gdmk_stencil8_geom(p, &tile_rows, &wgs_per_cu);
+  return tile_rows;
+}
+
 extern "C" hipError_t gdmk_launch_stencil(int p, int bk, const gdmk::StencilArgs &a, hipStream_t st) {
   using namespace gdmk;
-  switch (p) {
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 1
-    case 1: return GDM_LAUNCH7(1)(bk, a, st);
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 3
-    case 3: return GDM_LAUNCH7(3)(bk, a, st);
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 5
-    case 5: return GDM_LAUNCH7(5)(bk, a, st);
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 7
-    case 7: return GDM_LAUNCH7(7)(bk, a, st);
-#endif
-#if !defined(GDM_ONLY_P) || GDM_ONLY_P == 9
-    case 9: return GDM_LAUNCH7(9)(bk, a, st);
-#endif
-    
-    default: return hipErrorInvalidValue;
-  }
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, launch7_part, bk, a, st)
 }
-
-extern "C" hipError_t gdmk_launch_chol_lines(int p, double *v, int len, int64_t stride, int64_t n_lines, int64_t A,
-                                             int64_t B, int64_t C, const double *lrow, const double *inv_diag,
-                                             hipStream_t st) {
-  using namespace gdmk;
-  if (n_lines <= 0) return hipSuccess;
-  dim3 grid((unsigned)((n_lines + 255) / 256)), block(256);
-  switch (p) {
-    case 1: hipLaunchKernelGGL(chol_lines_kernel<1>, grid, block, 0, st, v, len, stride, n_lines, A, B, C, lrow, inv_diag); break;
-    case 3: hipLaunchKernelGGL(chol_lines_kernel<3>, grid, block, 0, st, v, len, stride, n_lines, A, B, C, lrow, inv_diag); break;
-    case 5: hipLaunchKernelGGL(chol_lines_kernel<5>, grid, block, 0, st, v, len, stride, n_lines, A, B, C, lrow, inv_diag); break;
-    case 7: hipLaunchKernelGGL(chol_lines_kernel<7>, grid, block, 0, st, v, len, stride, n_lines, A, B, C, lrow, inv_diag); break;
-    case 9: hipLaunchKernelGGL(chol_lines_kernel<9>, grid, block, 0, st, v, len, stride, n_lines, A, B, C, lrow, inv_diag); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-template <class Src, class Step2>
-static hipError_t face_launch(const gdmk::FaceArgs &f, const Src &U, hipStream_t st, Step2 &step2) {
-  using namespace gdmk;
-  const int n0 = f.i0_end - f.i0_begin;
-  const size_t cell_lds = sizeof(double) * ((size_t)f.p * (f.p + 1) * (f.p + 1) + (size_t)f.Q0);
-  if (f.phi0 && cell_lds <= 48 * 1024) {
-    // cell form of step 1, then the usual step 2
-    const int rpb = 4;
-    dim3 g1c((f.Q1 + rpb - 1) / rpb);
-    if (f.phase != 2) switch (f.p) {
-#define GDM_FACE_CELL(PP)                                                                                            \
-  case PP:                                                                                                         \
-    hipLaunchKernelGGL((face_cell_step1_kernel<PP, Src>), g1c, dim3(512), cell_lds, st, U, f.Q0, f.Q1, rpb, f.i0_begin, \
-                       n0, f.crange0, f.phi0, f.ncell0_total, f.cell0_begin, f.T);                                 \
-    break;
-      GDM_FACE_CELL(1) GDM_FACE_CELL(3) GDM_FACE_CELL(5) GDM_FACE_CELL(7) GDM_FACE_CELL(9)
-#undef GDM_FACE_CELL
-      default: return hipErrorInvalidValue;
-    }
-    dim3 g2((n0 + 255) / 256, f.i1_end - f.i1_begin);
-    if (f.phase != 1) step2(g2);
-    return hipGetLastError();
-  }
-  // rows per workgroup: as many as fit 48 KiB of LDS (up to 4)
-  const size_t row_bytes = sizeof(double) * (size_t)f.qmax0;
-  const int rows = row_bytes * 4 <= 48 * 1024 ? 4 : (row_bytes * 2 <= 48 * 1024 ? 2 : 1);
-  if (row_bytes > 48 * 1024) return hipErrorInvalidValue;  // <= (FACE_CHUNK + 2p) (p + 1) doubles in practice
-  dim3 g1((n0 + FACE_CHUNK - 1) / FACE_CHUNK, (f.Q1 + rows - 1) / rows);
-  const size_t lds = row_bytes * rows;
-  if (f.phase == 2)
-    ;
-  else if (rows == 4)
-    hipLaunchKernelGGL((face_step1_kernel<4, Src>), g1, dim3(FACE_CHUNK), lds, st, U, f.Q0, f.Q1, f.i0_begin, n0, f.qs0,
-                       f.w0T, f.wmax0, f.ldw0, f.qmax0, f.T);
-  else if (rows == 2)
-    hipLaunchKernelGGL((face_step1_kernel<2, Src>), g1, dim3(FACE_CHUNK), lds, st, U, f.Q0, f.Q1, f.i0_begin, n0, f.qs0,
-                       f.w0T, f.wmax0, f.ldw0, f.qmax0, f.T);
-  else
-    hipLaunchKernelGGL((face_step1_kernel<1, Src>), g1, dim3(FACE_CHUNK), lds, st, U, f.Q0, f.Q1, f.i0_begin, n0, f.qs0,
-                       f.w0T, f.wmax0, f.ldw0, f.qmax0, f.T);
-  dim3 g2((n0 + 255) / 256, f.i1_end - f.i1_begin);
-  if (f.phase != 1) step2(g2);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t gdmk_launch_face(const gdmk::FaceArgs &f, hipStream_t st) {
-  using namespace gdmk;
-  const int n0 = f.i0_end - f.i0_begin;
-  if (n0 <= 0 || f.Q1 <= 0 || f.i1_end <= f.i1_begin) return hipSuccess;
-  if (f.phase < 0 || f.phase > 2) return hipErrorInvalidValue;
-  auto step2 = [&](dim3 g2) {
-    hipLaunchKernelGGL(face_step2_kernel, g2, dim3(256), 0, st, f.T, n0, f.i1_begin, f.i1_end, f.qs1, f.qc1, f.w1,
-                       f.wmax1, f.dst, f.base, f.stride0, f.stride1, f.scale);
-  };
-  return face_launch(f, BcArr{f.U, f.Q0}, st, step2);
-}
-
-// step 1 (cell form) of n inflow faces in one launch (each face its own T)
-extern "C" hipError_t gdmk_launch_faces_step1(const gdmk::FaceArgs *fa, int n, hipStream_t st) {
-  using namespace gdmk;
-  if (n <= 0) return hipSuccess;
-  if (n > BcStage::kMaxFaces) return hipErrorNotSupported;
-  Step1Set<BcArr> s1{};
-  s1.rpb = 4;
-  size_t lds = 0;
-  int g1 = 0;
-  for (int i = 0; i < n; ++i) {
-    const FaceArgs &f = fa[i];
-    const size_t cell_lds = sizeof(double) * ((size_t)f.p * (f.p + 1) * (f.p + 1) + (size_t)f.Q0);
-    if (!f.phi0 || cell_lds > 48 * 1024 || !f.T || f.p != fa[0].p || f.Q1 <= 0 || f.i0_end <= f.i0_begin)
-      return hipErrorNotSupported;
-    for (int j = 0; j < i; ++j)
-      if (fa[j].T == f.T) return hipErrorNotSupported;  // faces must not share T
-    s1.f[i] = Step1Face<BcArr>{BcArr{f.U, f.Q0}, f.Q0, f.Q1, f.i0_begin, f.i0_end - f.i0_begin, f.crange0, f.phi0,
-                               f.ncell0_total, f.cell0_begin, f.T};
-    lds = std::max(lds, cell_lds);
-    g1 = std::max(g1, (f.Q1 + s1.rpb - 1) / s1.rpb);
-  }
-  switch (fa[0].p) {
-#define GDM_FACES_S1(PP)                                                                                       \
-  case PP:                                                                                                   \
-    hipLaunchKernelGGL((face_cell_step1_multi_kernel<PP, BcArr>), dim3(g1, n), dim3(512), lds, st, s1); \
-    break;
-    GDM_FACES_S1(1) GDM_FACES_S1(3) GDM_FACES_S1(5) GDM_FACES_S1(7) GDM_FACES_S1(9)
-#undef GDM_FACES_S1
-    default: return hipErrorNotSupported;
-  }
-  return hipGetLastError();
-}
-
-// step 2 of n inflow faces (their T from gdmk_launch_faces_step1) with the
-// ordered adds into dst, one launch (face_step2_add_kernel)
-extern "C" hipError_t gdmk_launch_faces_step2_add(const gdmk::FaceArgs *fa, const gdmk::FaceAddFace *fg, int n,
-                                                  int64_t N0, int64_t N1, int64_t own_off, double *dst,
-                                                  hipStream_t st) {
-  using namespace gdmk;
-  // rows per thread: 1 / 2 / 4 / 8 measured 41.5 / 37.0 / 45.6 / 74.9 us at C3
-  // (three 512^2 faces, profiles/r5_experiments/face_step2_rows.txt)
-  constexpr int kRows = 2;
-  if (n <= 0) return hipSuccess;
-  if (n > BcStage::kMaxFaces || N0 <= 0 || N1 <= 0) return hipErrorNotSupported;
-  Step2AddSet set{};
-  set.n = n;
-  set.N0 = N0;
-  set.N1 = N1;
-  set.own_off = own_off;
-  int gx = 0, gy = 0;
-  for (int i = 0; i < n; ++i) {
-    const FaceArgs &f = fa[i];
-    const int n0 = f.i0_end - f.i0_begin;
-    if (!f.T || fg[i].e0 - fg[i].b0 != n0 || fg[i].e1 - fg[i].b1 != f.i1_end - f.i1_begin) return hipErrorNotSupported;
-    set.f[i] = Step2Face{f.T, n0, f.i1_begin, f.i1_end, f.qs1, f.qc1, f.w1, f.wmax1, f.scale};
-    set.g[i] = fg[i];
-    gx = std::max(gx, (n0 + 63) / 64);
-    gy = std::max(gy, (f.i1_end - f.i1_begin + kRows - 1) / kRows);
-  }
-  if (gx <= 0 || gy <= 0) return hipSuccess;
-  hipLaunchKernelGGL(face_step2_add_kernel<kRows>, dim3(gx, gy, n), dim3(64), 0, st, set, dst);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t gdmk_launch_axpby(int64_t n, double a, const double *x, double b, double *y, hipStream_t st) {
-  using namespace gdmk;
-  if (n <= 0) return hipSuccess;
-  auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool pairs = al16(x) && al16(y);
-  int64_t blocks = ((pairs ? n / 2 : n) + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  const int mode = (a != 0.0 ? 1 : 0) | (b != 0.0 ? 2 : 0);
-#define GDM_AXPBY(M)                                                                                  \
-  case M:                                                                                             \
-    if (pairs)                                                                                        \
-      hipLaunchKernelGGL(axpby2_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, st, n, a, x, b, y); \
-    else                                                                                              \
-      hipLaunchKernelGGL(axpby_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, st, n, a, x, b, y);  \
-    break;
-  switch (mode) {
-    GDM_AXPBY(0)
-    GDM_AXPBY(1)
-    GDM_AXPBY(2)
-    GDM_AXPBY(3)
-  }
-#undef GDM_AXPBY
-  return hipGetLastError();
-}
-
-extern "C" hipError_t gdmk_launch_dot(int64_t n, const double *x, const double *y, double *partial, int n_partial,
-                                     double *out, hipStream_t st) {
-  using namespace gdmk;
-  hipLaunchKernelGGL(dot_partial_kernel, dim3(n_partial), dim3(256), 0, st, n, x, y, partial);
-  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, st, n_partial, partial, out);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t gdmk_launch_zero(int64_t n, double *y, hipStream_t st) {
-  using namespace gdmk;
-  if (n <= 0) return hipSuccess;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(zero_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, y);
-  return hipGetLastError();
-}
-#endif  // !GDM_STENCIL_PART
+#endif  // GDM_PART == 0

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gdm_parts.h"
+
 namespace gdmk {
 
 // Kernel geometry (the same for every degree): a workgroup of DIFF_TY / DIFF_RY
@@ -40,38 +42,21 @@ inline size_t diff_lds(int p, int n_terms) {
 
 }  // namespace gdmk
 
-// gdm_vardiff.hip compiles as one unit per degree (-DGDM_DIFF_PART=<p>); each
+// gdm_vardiff.hip compiles as one unit per degree (gdm_parts.h); each
 // defines its own two entry points, dispatched by degree below.
 //   prepare  raise the kernel's dynamic LDS limit to `lds` bytes on the current
 //            device (when the coefficient is set)
 //   apply    the kernel with `lds` bytes of dynamic LDS
-#define GDMK_DIFF_DECLARE(P)                      \
-  hipError_t gdmk_diff_prepare_p##P(size_t lds); \
-  hipError_t gdmk_diff_apply_p##P(const gdmk::DiffArgs &a, size_t lds, hipStream_t st);
 extern "C" {
-GDMK_DIFF_DECLARE(1)
-GDMK_DIFF_DECLARE(3)
-GDMK_DIFF_DECLARE(5)
-GDMK_DIFF_DECLARE(7)
-GDMK_DIFF_DECLARE(9)
+GDM_PARTS_DECLARE(gdmk_diff_prepare_p, size_t lds)
+GDM_PARTS_DECLARE(gdmk_diff_apply_p, const gdmk::DiffArgs &a, size_t lds, hipStream_t st)
 }
-#undef GDMK_DIFF_DECLARE
 
 namespace gdmk {
 
-#define GDMK_DIFF_SWITCH(fn, ...)                      \
-  switch (p) {                                         \
-    case 1: return gdmk_diff_##fn##_p1(__VA_ARGS__);   \
-    case 3: return gdmk_diff_##fn##_p3(__VA_ARGS__);   \
-    case 5: return gdmk_diff_##fn##_p5(__VA_ARGS__);   \
-    case 7: return gdmk_diff_##fn##_p7(__VA_ARGS__);   \
-    case 9: return gdmk_diff_##fn##_p9(__VA_ARGS__);   \
-    default: return hipErrorInvalidValue;              \
-  }
-inline hipError_t diff_prepare(int p, size_t lds) { GDMK_DIFF_SWITCH(prepare, lds) }
+inline hipError_t diff_prepare(int p, size_t lds) { GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_diff_prepare_p, lds) }
 inline hipError_t launch_diff(int p, const DiffArgs &a, size_t lds, hipStream_t st) {
-  GDMK_DIFF_SWITCH(apply, a, lds, st)
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_diff_apply_p, a, lds, st)
 }
-#undef GDMK_DIFF_SWITCH
 
 }  // namespace gdmk

@@ -2,7 +2,7 @@
 // coefficient kappa(x) = sum_t prod_d k_td(x_d) (gdm_op_set_coefficient;
 // DESIGN.md "Separable coefficient").
 //
-// One unit per degree: -DGDM_DIFF_PART=<p> (csrc/Makefile).
+// One unit per degree: -DGDM_PART=<p> (csrc/Makefile).
 //
 // wave/stiffness.h:171-181 and :296-310 with JxW multiplied by kappa at the
 // quadrature point: per term t
@@ -31,8 +31,8 @@
 
 #include "gdm_vardiff.h"
 
-#ifndef GDM_DIFF_PART
-#error "gdm_vardiff.hip is compiled per degree: -DGDM_DIFF_PART=<p>"
+#ifndef GDM_PART
+#error "gdm_vardiff.hip is compiled per degree: -DGDM_PART=<p>"
 #endif
 
 namespace {
@@ -153,29 +153,26 @@ std::atomic<size_t> g_lds_max{0};
 
 }  // namespace
 
-#define GDM_DIFF_CAT_(a, b) a##b
-#define GDM_DIFF_CAT(a, b) GDM_DIFF_CAT_(a, b)
-#define GDM_DIFF_NAME(stem) GDM_DIFF_CAT(stem, GDM_DIFF_PART)
 
 extern "C" {
 
-hipError_t GDM_DIFF_NAME(gdmk_diff_prepare_p)(size_t lds) {
+hipError_t GDM_PART_NAME(gdmk_diff_prepare_p)(size_t lds) {
   if (lds <= 64 * 1024) return hipSuccess;  // within the default limit
   // the limit is a property of the kernel, shared by every operator: keep the
   // largest request (set again on every call, so on every device that asks)
   size_t prev = g_lds_max.load();
   while (prev < lds && !g_lds_max.compare_exchange_weak(prev, lds)) {
   }
-  return hipFuncSetAttribute((const void *)diff_kernel<GDM_DIFF_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute((const void *)diff_kernel<GDM_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)g_lds_max.load());
 }
 
-hipError_t GDM_DIFF_NAME(gdmk_diff_apply_p)(const gdmk::DiffArgs &a, size_t lds, hipStream_t st) {
+hipError_t GDM_PART_NAME(gdmk_diff_apply_p)(const gdmk::DiffArgs &a, size_t lds, hipStream_t st) {
   if (a.Nx <= 0 || a.Ny <= 0 || a.Nz <= 0 || a.n_terms <= 0) return hipSuccess;
   if (a.n_terms > gdmk::DIFF_MAX_TERMS) return hipErrorInvalidValue;
   const dim3 grid((a.Nx + DIFF_TX - 1) / DIFF_TX, (a.Ny + DIFF_TY - 1) / DIFF_TY, (a.Nz + DIFF_ZC - 1) / DIFF_ZC);
   if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(diff_kernel<GDM_DIFF_PART>, grid, dim3(DIFF_THREADS), lds, st, a);
+  hipLaunchKernelGGL(diff_kernel<GDM_PART>, grid, dim3(DIFF_THREADS), lds, st, a);
   return hipGetLastError();
 }
 

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gdm_parts.h"
+
 namespace gdmk {
 
 // Kernel geometry (the same for every degree, and the same as gdm_vardiff.h):
@@ -43,38 +45,21 @@ inline size_t varmass_lds(int p, int n_terms) {
 
 }  // namespace gdmk
 
-// gdm_varmass.hip compiles as one unit per degree (-DGDM_VMASS_PART=<p>); each
+// gdm_varmass.hip compiles as one unit per degree (gdm_parts.h); each
 // defines its own two entry points, dispatched by degree below.
 //   prepare  raise the kernel's dynamic LDS limit to `lds` bytes on the current
 //            device (when the density is set)
 //   apply    the kernel with `lds` bytes of dynamic LDS
-#define GDMK_VMASS_DECLARE(P)                      \
-  hipError_t gdmk_vmass_prepare_p##P(size_t lds); \
-  hipError_t gdmk_vmass_apply_p##P(const gdmk::VarMassArgs &a, size_t lds, hipStream_t st);
 extern "C" {
-GDMK_VMASS_DECLARE(1)
-GDMK_VMASS_DECLARE(3)
-GDMK_VMASS_DECLARE(5)
-GDMK_VMASS_DECLARE(7)
-GDMK_VMASS_DECLARE(9)
+GDM_PARTS_DECLARE(gdmk_vmass_prepare_p, size_t lds)
+GDM_PARTS_DECLARE(gdmk_vmass_apply_p, const gdmk::VarMassArgs &a, size_t lds, hipStream_t st)
 }
-#undef GDMK_VMASS_DECLARE
 
 namespace gdmk {
 
-#define GDMK_VMASS_SWITCH(fn, ...)                      \
-  switch (p) {                                          \
-    case 1: return gdmk_vmass_##fn##_p1(__VA_ARGS__);   \
-    case 3: return gdmk_vmass_##fn##_p3(__VA_ARGS__);   \
-    case 5: return gdmk_vmass_##fn##_p5(__VA_ARGS__);   \
-    case 7: return gdmk_vmass_##fn##_p7(__VA_ARGS__);   \
-    case 9: return gdmk_vmass_##fn##_p9(__VA_ARGS__);   \
-    default: return hipErrorInvalidValue;               \
-  }
-inline hipError_t varmass_prepare(int p, size_t lds) { GDMK_VMASS_SWITCH(prepare, lds) }
+inline hipError_t varmass_prepare(int p, size_t lds) { GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_vmass_prepare_p, lds) }
 inline hipError_t launch_varmass(int p, const VarMassArgs &a, size_t lds, hipStream_t st) {
-  GDMK_VMASS_SWITCH(apply, a, lds, st)
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_vmass_apply_p, a, lds, st)
 }
-#undef GDMK_VMASS_SWITCH
 
 }  // namespace gdmk

@@ -2,7 +2,7 @@
 // rho(x) = sum_t prod_d r_td(x_d) (gdm_op_set_density; DESIGN.md "Separable
 // density").
 //
-// One unit per degree: -DGDM_VMASS_PART=<p> (csrc/Makefile).
+// One unit per degree: -DGDM_PART=<p> (csrc/Makefile).
 //
 // wave/mass.h:47-249 with JxW multiplied by rho at the quadrature point: per
 // term t
@@ -30,8 +30,8 @@
 
 #include "gdm_varmass.h"
 
-#ifndef GDM_VMASS_PART
-#error "gdm_varmass.hip is compiled per degree: -DGDM_VMASS_PART=<p>"
+#ifndef GDM_PART
+#error "gdm_varmass.hip is compiled per degree: -DGDM_PART=<p>"
 #endif
 
 namespace {
@@ -135,30 +135,27 @@ std::atomic<size_t> g_lds_max{0};
 
 }  // namespace
 
-#define GDM_VMASS_CAT_(a, b) a##b
-#define GDM_VMASS_CAT(a, b) GDM_VMASS_CAT_(a, b)
-#define GDM_VMASS_NAME(stem) GDM_VMASS_CAT(stem, GDM_VMASS_PART)
 
 extern "C" {
 
-hipError_t GDM_VMASS_NAME(gdmk_vmass_prepare_p)(size_t lds) {
+hipError_t GDM_PART_NAME(gdmk_vmass_prepare_p)(size_t lds) {
   if (lds <= 64 * 1024) return hipSuccess;  // within the default limit
   // the limit is a property of the kernel, shared by every operator: keep the
   // largest request (set again on every call, so on every device that asks)
   size_t prev = g_lds_max.load();
   while (prev < lds && !g_lds_max.compare_exchange_weak(prev, lds)) {
   }
-  return hipFuncSetAttribute((const void *)varmass_kernel<GDM_VMASS_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute((const void *)varmass_kernel<GDM_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)g_lds_max.load());
 }
 
-hipError_t GDM_VMASS_NAME(gdmk_vmass_apply_p)(const gdmk::VarMassArgs &a, size_t lds, hipStream_t st) {
+hipError_t GDM_PART_NAME(gdmk_vmass_apply_p)(const gdmk::VarMassArgs &a, size_t lds, hipStream_t st) {
   if (a.Nx <= 0 || a.Ny <= 0 || a.Nz <= 0 || a.n_terms <= 0) return hipSuccess;
   if (a.n_terms > gdmk::VMASS_MAX_TERMS) return hipErrorInvalidValue;
   const dim3 grid((a.Nx + VMASS_TX - 1) / VMASS_TX, (a.Ny + VMASS_TY - 1) / VMASS_TY,
                   (a.Nz + VMASS_ZC - 1) / VMASS_ZC);
   if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(varmass_kernel<GDM_VMASS_PART>, grid, dim3(VMASS_THREADS), lds, st, a);
+  hipLaunchKernelGGL(varmass_kernel<GDM_PART>, grid, dim3(VMASS_THREADS), lds, st, a);
   return hipGetLastError();
 }
 

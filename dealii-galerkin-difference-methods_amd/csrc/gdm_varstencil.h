@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gdm_parts.h"
+
 namespace gdmk {
 
 // Volume kernel geometry: one workgroup of VAR_TX * VAR_TY threads owns an
@@ -57,25 +59,18 @@ struct VarFaceArgs {
 
 }  // namespace gdmk
 
-// gdm_varstencil.hip compiles as one unit per degree (-DGDM_VAR_PART=<p>); each
+// gdm_varstencil.hip compiles as one unit per degree (gdm_parts.h); each
 // defines its own three entry points, dispatched by degree below.
 //   prepare  raise the volume kernel's dynamic LDS limit to `lds` bytes on the
 //            current device (once, when the launch plan is built)
 //   volume   the volume kernel with `lds` bytes of dynamic LDS
 //   face     the three launches of one box face (points, t0 projection, t1
 //            projection + add into dst), stream-ordered
-#define GDMK_VAR_DECLARE(P)                                                                      \
-  hipError_t gdmk_var_prepare_p##P(size_t lds);                                                  \
-  hipError_t gdmk_var_volume_p##P(const gdmk::VarArgs &a, size_t lds, hipStream_t st);           \
-  hipError_t gdmk_var_face_p##P(const gdmk::VarFaceArgs &f, hipStream_t st);
 extern "C" {
-GDMK_VAR_DECLARE(1)
-GDMK_VAR_DECLARE(3)
-GDMK_VAR_DECLARE(5)
-GDMK_VAR_DECLARE(7)
-GDMK_VAR_DECLARE(9)
+GDM_PARTS_DECLARE(gdmk_var_prepare_p, size_t lds)
+GDM_PARTS_DECLARE(gdmk_var_volume_p, const gdmk::VarArgs &a, size_t lds, hipStream_t st)
+GDM_PARTS_DECLARE(gdmk_var_face_p, const gdmk::VarFaceArgs &f, hipStream_t st)
 }
-#undef GDMK_VAR_DECLARE
 
 namespace gdmk {
 
@@ -86,20 +81,12 @@ inline size_t var_volume_lds(int p, int n_x, int n_xy) {
   return sizeof(double) * (SY * SX + (size_t)n_x * SY * VAR_TX + (size_t)n_x * VAR_TX * W + (size_t)n_xy * VAR_TY * W);
 }
 
-#define GDMK_VAR_SWITCH(fn, ...)                              \
-  switch (p) {                                                \
-    case 1: return gdmk_var_##fn##_p1(__VA_ARGS__);           \
-    case 3: return gdmk_var_##fn##_p3(__VA_ARGS__);           \
-    case 5: return gdmk_var_##fn##_p5(__VA_ARGS__);           \
-    case 7: return gdmk_var_##fn##_p7(__VA_ARGS__);           \
-    case 9: return gdmk_var_##fn##_p9(__VA_ARGS__);           \
-    default: return hipErrorInvalidValue;                     \
-  }
-inline hipError_t var_prepare(int p, size_t lds) { GDMK_VAR_SWITCH(prepare, lds) }
+inline hipError_t var_prepare(int p, size_t lds) { GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_var_prepare_p, lds) }
 inline hipError_t launch_var_volume(int p, const VarArgs &a, size_t lds, hipStream_t st) {
-  GDMK_VAR_SWITCH(volume, a, lds, st)
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_var_volume_p, a, lds, st)
 }
-inline hipError_t launch_var_face(int p, const VarFaceArgs &f, hipStream_t st) { GDMK_VAR_SWITCH(face, f, st) }
-#undef GDMK_VAR_SWITCH
+inline hipError_t launch_var_face(int p, const VarFaceArgs &f, hipStream_t st) {
+  GDM_PARTS_SWITCH(p, hipErrorInvalidValue, gdmk_var_face_p, f, st)
+}
 
 }  // namespace gdmk

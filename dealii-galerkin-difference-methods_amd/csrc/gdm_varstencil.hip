@@ -1,7 +1,7 @@
 // gdm_varstencil.hip -- advection with a separable, spatially varying velocity
 // field (gdm_op_set_advection_field; DESIGN.md "Separable fields").
 //
-// One unit per degree: -DGDM_VAR_PART=<p> (csrc/Makefile).
+// One unit per degree: -DGDM_PART=<p> (csrc/Makefile).
 //
 // Volume:  dst = sum_t s_t (A^t_x (x) A^t_y (x) A^t_z) src, the quadrature sums
 // of advection/stiffness.h:395-417 reordered, with A = C[f] along the term's
@@ -33,8 +33,8 @@
 
 #include "gdm_varstencil.h"
 
-#ifndef GDM_VAR_PART
-#error "gdm_varstencil.hip is compiled per degree: -DGDM_VAR_PART=<p>"
+#ifndef GDM_PART
+#error "gdm_varstencil.hip is compiled per degree: -DGDM_PART=<p>"
 #endif
 
 namespace {
@@ -205,36 +205,33 @@ std::atomic<size_t> g_lds_max{0};
 
 }  // namespace
 
-#define GDM_VAR_CAT_(a, b) a##b
-#define GDM_VAR_CAT(a, b) GDM_VAR_CAT_(a, b)
-#define GDM_VAR_NAME(stem) GDM_VAR_CAT(stem, GDM_VAR_PART)
 
 extern "C" {
 
-hipError_t GDM_VAR_NAME(gdmk_var_prepare_p)(size_t lds) {
+hipError_t GDM_PART_NAME(gdmk_var_prepare_p)(size_t lds) {
   if (lds <= 64 * 1024) return hipSuccess;  // within the default limit
   // the limit is a property of the kernel, shared by every operator: keep the
   // largest request (set again on every call, so on every device that asks)
   size_t prev = g_lds_max.load();
   while (prev < lds && !g_lds_max.compare_exchange_weak(prev, lds)) {
   }
-  return hipFuncSetAttribute((const void *)var_volume_kernel<GDM_VAR_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute((const void *)var_volume_kernel<GDM_PART>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)g_lds_max.load());
 }
 
-hipError_t GDM_VAR_NAME(gdmk_var_volume_p)(const gdmk::VarArgs &a, size_t lds, hipStream_t st) {
+hipError_t GDM_PART_NAME(gdmk_var_volume_p)(const gdmk::VarArgs &a, size_t lds, hipStream_t st) {
   if (a.Nx <= 0 || a.Ny <= 0 || a.Nz <= 0) return hipSuccess;
   const dim3 grid((a.Nx + VAR_TX - 1) / VAR_TX, (a.Ny + VAR_TY - 1) / VAR_TY, (a.Nz + VAR_ZC - 1) / VAR_ZC);
   if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(var_volume_kernel<GDM_VAR_PART>, grid, dim3(VAR_THREADS), lds, st, a);
+  hipLaunchKernelGGL(var_volume_kernel<GDM_PART>, grid, dim3(VAR_THREADS), lds, st, a);
   return hipGetLastError();
 }
 
-hipError_t GDM_VAR_NAME(gdmk_var_face_p)(const gdmk::VarFaceArgs &f, hipStream_t st) {
+hipError_t GDM_PART_NAME(gdmk_var_face_p)(const gdmk::VarFaceArgs &f, hipStream_t st) {
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   const int64_t npts = (int64_t)f.Q0 * f.Q1, nT = (int64_t)f.n0 * f.Q1, nn = (int64_t)f.n0 * f.n1;
   if (npts <= 0 || nn <= 0) return hipSuccess;
-  hipLaunchKernelGGL(var_face_points_kernel<GDM_VAR_PART>, blocks(npts), dim3(256), 0, st, f);
+  hipLaunchKernelGGL(var_face_points_kernel<GDM_PART>, blocks(npts), dim3(256), 0, st, f);
   hipLaunchKernelGGL(var_face_t0_kernel, blocks(nT), dim3(256), 0, st, f);
   hipLaunchKernelGGL(var_face_t1_kernel, blocks(nn), dim3(256), 0, st, f);
   return hipGetLastError();

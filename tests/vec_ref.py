@@ -12,7 +12,7 @@ import numpy as np
 
 U = 2.0 ** -53  # unit roundoff of binary64
 N_DOT_PARTIAL = 1024  # gdm_op::n_dot_partial (csrc/gdm_capi_internal.h): the cap of gdm_vec_dot's partial blocks
-DOT_BLOCK = 256  # lanes per block of dot_partial_kernel / dot_final_kernel (csrc/gdm_kernels.hip)
+DOT_BLOCK = 256  # lanes per block of dot_partial_kernel / dot_final_kernel (csrc/gdm_vec.hip)
 
 
 def axpby_ref(a, x, b, y):
@@ -54,7 +54,7 @@ def dot_ref(x, y):
 def dot_bound(n, sum_abs):
     """|device - dot_ref| <= (ceil(n / (256 np)) + 32) 2^-53 sum |x_i y_i|, np = dot_n_blocks(n).
 
-    Derivation (csrc/gdm_kernels.hip).  dot_partial_kernel: lane l of block b
+    Derivation (csrc/gdm_vec.hip).  dot_partial_kernel: lane l of block b
     folds its m = ceil(n / (256 np)) entries i = 256 b + l + 256 np j into
     s = fma(x_i, y_i, s): m roundings on the path of an entry (the product is
     not rounded).  wave_sum adds 6 levels, the four wave sums 3 more additions.
