@@ -1346,6 +1346,7 @@ int gdm_op_create(const gdm_mesh_desc *mesh, int kind, const double *params, int
   build_faces(op);
   if (mesh->periodic) build_periodic_mass(op);
   if (mesh->n_ranks == 1 && !mesh->periodic) build_load(op);
+  if (mesh->n_ranks == 1 && !mesh->periodic) build_evalgrid(op);
   if (kind == GDM_OP_ELASTICITY) build_elasticity(op);
   op->zchunk = choose_zchunk(op);
   hip_check(hipMalloc(&op->dot_partial, sizeof(double) * op->n_dot_partial), "hipMalloc");
@@ -2488,7 +2489,7 @@ int gdm_error_norms_grid(gdm_op *op, const double *u_local, const double *exact_
 
 }  // extern "C"
 
-namespace {
+namespace gdm_detail {
 
 // shared checks of the data-term entry points; 0 = ok
 int check_load_op(gdm_op *op, const char *what) {
@@ -2520,7 +2521,7 @@ gdmk::LoadGeom load_geom(const gdm_op *op) {
   return g;
 }
 
-}  // namespace
+}  // namespace gdm_detail
 
 extern "C" {
 

@@ -171,14 +171,16 @@ void coef_grid_tables(int p, unsigned ncell, double h, CoefGridTables &T) {
   }
 }
 
-// The kernel axes of the tensor Gauss grid (gdm_coefgrid.hip, gdm_massgrid.hip)
-// into ax[3], every uploaded table recorded in `made`; a tile's footprint
-// is checked against the kernel's compile-time bounds (tile, Gauss points and
-// node span of kernel axes x and y).  Returns the volume of the box.
-double build_grid_axes(gdm_op *op, const int tile[2], const int nq_max[2], const int span_max[2], const char *what,
-                       std::vector<void *> &made, gdmk::CgAxis ax[3]) {
+}  // namespace
+
+// The kernel axes of the tensor Gauss grid, built once per operator by
+// gdm_op_create (single rank, non-periodic) into op->ev: the device tables that
+// gdm_coefgrid.hip, gdm_massgrid.hip and gdm_evalgrid.hip share, host copies of
+// the box offsets and point ranges for the footprint checks, the box volume.
+void gdm_detail::build_grid_axes(gdm_op *op) {
   const int p = op->p, n1 = p + 1;
-  double volume = 1.0;
+  gdm_op::Eval &ev = op->ev;
+  ev.volume = 1.0;
   for (int k = 0; k < 3; ++k) {
     const int d = op->kdir[k];
     CoefGridTables T;
@@ -193,7 +195,7 @@ double build_grid_axes(gdm_op *op, const int tile[2], const int nq_max[2], const
       const unsigned ncell = (unsigned)op->mesh.n_subdivisions[d];
       coef_grid_tables(p, ncell, (op->mesh.hi[d] - op->mesh.lo[d]) / ncell, T);
       N = op->N[d];
-      volume *= op->mesh.hi[d] - op->mesh.lo[d];
+      ev.volume *= op->mesh.hi[d] - op->mesh.lo[d];
     }
     const int Q = (int)T.first.size();
     // the Gauss points whose box holds node i: a contiguous range (the boxes move monotonically)
@@ -203,26 +205,44 @@ double build_grid_axes(gdm_op *op, const int tile[2], const int nq_max[2], const
         qlo[(size_t)i] = std::min(qlo[(size_t)i], q);
         qhi[(size_t)i] = std::max(qhi[(size_t)i], q + 1);
       }
-    // the kernel's compile-time bounds on a tile's footprint
+    gdmk::CgAxis &A = ev.ax[k];
+    A.N = N;
+    A.Q = Q;
+    A.first = keep(op, dev_upload(T.first));
+    A.val = keep(op, dev_upload(T.val));
+    A.der = keep(op, dev_upload(T.der));
+    A.w = keep(op, dev_upload(T.w));
+    A.qlo = keep(op, dev_upload(qlo));
+    A.qhi = keep(op, dev_upload(qhi));
+    ev.first[k] = std::move(T.first);
+    ev.qlo[k] = std::move(qlo);
+    ev.qhi[k] = std::move(qhi);
+  }
+}
+
+// The operator's kernel axes into ax[3] for a kernel with compile-time bounds
+// on a tile's footprint (tile, Gauss points and node span of kernel axes x and
+// y), which are checked here.  Returns the volume of the box.
+double gdm_detail::grid_axes(const gdm_op *op, const int tile[2], const int nq_max[2], const int span_max[2],
+                             const char *what, gdmk::CgAxis ax[3]) {
+  const gdm_op::Eval &ev = op->ev;
+  if (ev.first[0].empty()) throw std::runtime_error(std::string(what) + ": the operator has no grid axes");
+  for (int k = 0; k < 3; ++k) {
+    const int N = ev.ax[k].N, p = op->p;
+    const std::vector<int32_t> &first = ev.first[k], &qlo = ev.qlo[k], &qhi = ev.qhi[k];
     for (int i0 = 0; i0 < N && k < 2; i0 += tile[k]) {
       const int il = std::min(N, i0 + tile[k]) - 1;
       const int q0 = qlo[(size_t)i0], q1 = qhi[(size_t)il];
-      const int span = std::min(T.first[(size_t)q1 - 1] + p, N - 1) - T.first[(size_t)q0] + 1;
+      const int span = std::min(first[(size_t)q1 - 1] + p, N - 1) - first[(size_t)q0] + 1;
       if (q1 <= q0 || q1 - q0 > nq_max[k] || span > span_max[k])
         throw std::runtime_error(std::string(what) + ": a tile's footprint exceeds the kernel's bounds");
     }
-    gdmk::CgAxis &A = ax[k];
-    A.N = N;
-    A.Q = Q;
-    A.first = up(made, T.first);
-    A.val = up(made, T.val);
-    A.der = up(made, T.der);
-    A.w = up(made, T.w);
-    A.qlo = up(made, qlo);
-    A.qhi = up(made, qhi);
+    ax[k] = ev.ax[k];
   }
-  return volume;
+  return ev.volume;
 }
+
+namespace {
 
 // One reduction over n samples on the operator's stream: the Gauss-weighted sum
 // into *sum (axes_dev NULL: the samples carry no weights, the sum means nothing)
@@ -257,7 +277,7 @@ bool build_coef_grid(gdm_op *op, const double *kq, const double *kbc, gdm_op::Co
   a.kq = kq;
   const int tile[2] = {gdmk::cg_tx(p), gdmk::cg_ty(p)}, nq_max[2] = {gdmk::cg_nqx(p), gdmk::cg_nqy(p)},
             span_max[2] = {gdmk::cg_sx(p), gdmk::cg_sy(p)};
-  const double volume = build_grid_axes(op, tile, nq_max, span_max, "grid coefficient", nc.allocations, a.ax);
+  const double volume = grid_axes(op, tile, nq_max, span_max, "grid coefficient", a.ax);
   hip_check(gdmk::cg_prepare(p), "grid coefficient: LDS limit");
 
   // the box faces (Nitsche part)
@@ -495,7 +515,7 @@ bool build_density_grid(gdm_op *op, const double *rq, gdm_op::Density &nd) {
   a.rq = rq;
   const int tile[2] = {gdmk::mg_tx(p), gdmk::mg_ty(p)}, nq_max[2] = {gdmk::mg_nqx(p), gdmk::mg_nqy(p)},
             span_max[2] = {gdmk::mg_sx(p), gdmk::mg_sy(p)};
-  const double volume = build_grid_axes(op, tile, nq_max, span_max, "grid density", nd.allocations, a.ax);
+  const double volume = grid_axes(op, tile, nq_max, span_max, "grid density", a.ax);
   if ((int64_t)a.ax[0].N * a.ax[1].N * a.ax[2].N != op->layout.n_owned)
     throw std::runtime_error("grid density: the kernel axes do not cover the owned DoFs");
   int n_cu = 0;

@@ -16,6 +16,7 @@
 #include "../../include/gdm_hip.h"
 #include "gdm_coefgrid.h"
 #include "gdm_elasticity.h"
+#include "gdm_evalgrid.h"
 #include "gdm_kernels.h"
 #include "gdm_massgrid.h"
 #include "gdm_pcg.h"
@@ -258,6 +259,20 @@ struct gdm_op {
   // the per-axis (sin, cos) load vectors of the rank-1 path [3][2][load_ld]
   double *load_Sw = nullptr, *load_bvec = nullptr;
   int load_ld = 0;
+  // the tensor Gauss grid (single rank, non-periodic; build_grid_axes): the
+  // kernel axes that the grid coefficient, the grid density and the grid
+  // evaluation share, with host copies of the box offsets and point ranges and
+  // the box volume; for gdm_eval_grid, gdm_add_load_grad and gdm_eval_trace the
+  // derivative tables times quadrature weights per category next to load_Sw
+  // and the box faces
+  struct Eval {
+    bool built = false;
+    gdmk::CgAxis ax[3]{};
+    std::vector<int32_t> first[3], qlo[3], qhi[3];
+    double volume = 1.0;
+    double *Dw = nullptr;
+    std::vector<gdmk::EvFace> faces;
+  } ev;
   // fast diagonalisation (gdm_system_solve_setup): per kernel axis the tables
   // S and S^T (row-major N x N) and lambda, the eigenvalue extremes for the
   // host check of a solve, two scratch vectors
@@ -399,12 +414,20 @@ hipError_t launch_stencil(gdm_op *op, bool mass, const double *src, double *dst,
                           const gdmk::FaceArgs *tail = nullptr, int n_tail = 0, bool *tail_done = nullptr,
                           int zb2 = 0, int ze2 = 0);
 void any_stencil(gdm_op *op, bool mass, const double *src, double *dst);
+int check_load_op(gdm_op *op, const char *what);
+gdmk::LoadGeom load_geom(const gdm_op *op);
 bool mass_solve_passes(gdm_op *op, const double *rhs_owned, double *x_owned, const LineTables *part,
                        const gdmk::RkOut *rk = nullptr, const LineTables *const *axis_tab = nullptr);
 
 // ---- gdm_capi_coef.cpp ----
 void coef_apply(gdm_op *op, const double *src, double *dst);
+void build_grid_axes(gdm_op *op);
+double grid_axes(const gdm_op *op, const int tile[2], const int nq_max[2], const int span_max[2], const char *what,
+                 gdmk::CgAxis ax[3]);
 gdmk::FastdiagPass fastdiag_pass(const gdm_op *op, int ax, const double *Tt);  // gdm_fastdiag.h
+
+// ---- gdm_capi_evalgrid.cpp ----
+void build_evalgrid(gdm_op *op);
 
 // ---- gdm_capi_elasticity.cpp ----
 void build_elasticity(gdm_op *op);

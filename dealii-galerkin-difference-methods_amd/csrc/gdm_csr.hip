@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(CSR_BLOCK) csr_spmv_kernel(int64_t n_rows, con
   if (row < n_rows && l == 0) {
     if (b) s = b[row] - s;
     y[row] = s;
-    d = x[row] * s;
+    if (partial) d = x[row] * s;  // x has n_cols entries: x[row] exists for a square A only
   }
   if (partial) {
     const double t = block_sum(d, sh);
@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(CSR_BLOCK) csr_rowblock_kernel(const int64_t *
     if (threadIdx.x == 0) {
       if (b) s = b[r0] - s;
       y[r0] = s;
-      d = x[r0] * s;
+      if (partial) d = x[r0] * s;
     }
   } else {
     const int nz = (int)(k1 - k0);
@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(CSR_BLOCK) csr_rowblock_kernel(const int64_t *
       for (int k = a; k < e; ++k) s += prod[k];
       if (b) s = b[row] - s;
       y[row] = s;
-      d = x[row] * s;
+      if (partial) d = x[row] * s;
     }
   }
   if (partial) {

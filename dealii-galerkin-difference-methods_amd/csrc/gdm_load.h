@@ -30,6 +30,24 @@ struct LoadGeom {
   double xq[10];
 };
 
+// the index helpers of the gather kernels (load_kernel; ev_flux_kernel of gdm_evalgrid.hip)
+#ifdef __HIPCC__
+// cell category / DoF box offset / cells whose box holds node i (odd p, n >= p)
+__device__ __forceinline__ int ld_cat(int c, int p, int n) {
+  const int half = p / 2;
+  if (c < half) return c;
+  if (c < n - half) return half;
+  return p + c - n;
+}
+__device__ __forceinline__ int ld_off(int c, int p, int n) {
+  const int half = p / 2;
+  if (c < half) return 0;
+  return min(n, c + half + 1) - p;
+}
+__device__ __forceinline__ int ld_first(int i, int p, int n) { return i <= p ? 0 : i - p + p / 2; }
+__device__ __forceinline__ int ld_last(int i, int p, int n) { return i >= n - p ? n - 1 : i + p / 2; }
+#endif
+
 // One box face of the Dirichlet data term: the tangential projection tables
 // (FaceTable of gdm_setup.h: w includes the face JxW factor of its direction)
 // and the p + 1 node planes behind the face with their weights

@@ -27,25 +27,6 @@
 
 namespace gdmk {
 
-namespace {
-
-// cell category / DoF box offset / cells whose box holds node i (odd p, n >= p)
-__device__ __forceinline__ int ld_cat(int c, int p, int n) {
-  const int half = p / 2;
-  if (c < half) return c;
-  if (c < n - half) return half;
-  return p + c - n;
-}
-__device__ __forceinline__ int ld_off(int c, int p, int n) {
-  const int half = p / 2;
-  if (c < half) return 0;
-  return min(n, c + half + 1) - p;
-}
-__device__ __forceinline__ int ld_first(int i, int p, int n) { return i <= p ? 0 : i - p + p / 2; }
-__device__ __forceinline__ int ld_last(int i, int p, int n) { return i >= n - p ? n - 1 : i + p / 2; }
-
-}  // namespace
-
 template <int P, int MODE>
 __global__ void __launch_bounds__(LOAD_TX *LOAD_TY) load_kernel(LoadGeom g, BcFn f, const double *__restrict__ Sw,
                                                                   const double *__restrict__ fq, double scale,

@@ -207,6 +207,11 @@ def load():
         "gdm_load_vector_1d": [ctypes.POINTER(MeshDesc), i32, P, P],
         "gdm_load_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                           ctypes.POINTER(ctypes.c_int)],
+        "gdm_eval_grid": [P, P, P, P],
+        "gdm_add_load_grad": [P, P, d, P],
+        "gdm_eval_trace": [P, P, P, P],
+        "gdm_eval_grid_tile": [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                               ctypes.POINTER(ctypes.c_int)],
         "gdm_fastdiag_tables": [ctypes.POINTER(MeshDesc), d, i32, P, P],
         "gdm_system_solve_setup": [P],
         "gdm_system_solve": [P, d, d, P, P],
@@ -518,6 +523,14 @@ def load_tile(fe_degree, dim=3):
     """(tile_x, tile_y, z_chunk) of the general load kernel, kernel axes (gdm_load_tile)"""
     t = [ctypes.c_int(0) for _ in range(3)]
     check(load().gdm_load_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_load_tile")
+    return tuple(v.value for v in t)
+
+
+def eval_grid_tile(fe_degree, dim=3):
+    """(cells_x, cells_y, cells_z) of one work item of the grid evaluation kernel, kernel axes
+    (gdm_eval_grid_tile)"""
+    t = [ctypes.c_int(0) for _ in range(3)]
+    check(load().gdm_eval_grid_tile(int(fe_degree), int(dim), *[ctypes.byref(v) for v in t]), "gdm_eval_grid_tile")
     return tuple(v.value for v in t)
 
 

@@ -403,6 +403,82 @@ class GdmOperator:
         """(tile_x, tile_y, z_chunk) of the general load kernel, kernel axes"""
         return _capi.load_tile(self.p, self.dim)
 
+    # -- grid evaluation: u, grad u, the flux load and the wall trace ---------------
+    @property
+    def n_grid_points(self):
+        """Q = prod_d n_sub_d (p + 1), the points of the tensor Gauss grid"""
+        nq = 1
+        for d in range(self.dim):
+            nq *= self.mesh.n_subdivisions[d] * (self.p + 1)
+        return nq
+
+    def _new(self, n):
+        return self._torch.empty(n, dtype=self._torch.float64, device="cuda:%d" % self.device)
+
+    def eval_grid(self, u, values=None, gradients=None):
+        """u and its physical gradient at the Gauss points (gdm_eval_grid;
+        FEValues::get_function_values / get_function_gradients): values[Q] in
+        add_load's layout, gradients[dim Q] component-major (gradients[e Q + q],
+        e the reference direction).  values=False / gradients=False leaves that
+        output out (it then costs nothing); None allocates it.  u is one
+        component's vector (elasticity: GdmOperator.component).  Returns
+        (values, gradients), the values alone with gradients=False, the
+        gradients alone with values=False."""
+        if u.numel() != self.n_local:
+            raise GdmError("eval_grid: u has %d entries, expected n_local %d" % (u.numel(), self.n_local))
+        nq = self.n_grid_points
+        if values is None:
+            values = self._new(nq)
+        if gradients is None:
+            gradients = self._new(self.dim * nq)
+        want_v, want_g = values is not False, gradients is not False
+        if want_v and values.numel() != nq:
+            raise GdmError("eval_grid: values has %d entries, the quadrature grid %d" % (values.numel(), nq))
+        if want_g and gradients.numel() != self.dim * nq:
+            raise GdmError("eval_grid: gradients has %d entries, expected %d" % (gradients.numel(), self.dim * nq))
+        check(self.lib.gdm_eval_grid(self.h, _ptr(u), _ptr(values) if want_v else None,
+                                     _ptr(gradients) if want_g else None), "gdm_eval_grid")
+        if want_v and want_g:
+            return values, gradients
+        return values if want_v else gradients
+
+    def add_load_grad(self, Fq, dst_owned, scale=1.0):
+        """dst += scale sum_e (d_e v, F_e) over QGauss(p+1), Fq[dim Q]
+        component-major on the tensor Gauss grid (gdm_add_load_grad): the
+        transpose of eval_grid's gradients with the Gauss weights"""
+        self._check_sizes(None, dst_owned)
+        if Fq.numel() != self.dim * self.n_grid_points:
+            raise GdmError("add_load_grad: Fq has %d entries, expected %d" % (Fq.numel(),
+                                                                             self.dim * self.n_grid_points))
+        check(self.lib.gdm_add_load_grad(self.h, _ptr(Fq), float(scale), _ptr(dst_owned)), "gdm_add_load_grad")
+        return dst_owned
+
+    def eval_trace(self, u, u_bc=None, dn_bc=None):
+        """the wall trace and the outward normal derivative of u at the
+        n_bc_points boundary points, device block(0) order (gdm_eval_trace).
+        u_bc=False / dn_bc=False leaves that output out; None allocates it.
+        Returns (u_bc, dn_bc), or the one that was asked for."""
+        if u.numel() != self.n_local:
+            raise GdmError("eval_trace: u has %d entries, expected n_local %d" % (u.numel(), self.n_local))
+        n = self.n_bc_points
+        if u_bc is None:
+            u_bc = self._new(n)
+        if dn_bc is None:
+            dn_bc = self._new(n)
+        want_u, want_d = u_bc is not False, dn_bc is not False
+        for name, t, want in (("u_bc", u_bc, want_u), ("dn_bc", dn_bc, want_d)):
+            if want and t.numel() != n:
+                raise GdmError("eval_trace: %s has %d entries, expected %d" % (name, t.numel(), n))
+        check(self.lib.gdm_eval_trace(self.h, _ptr(u), _ptr(u_bc) if want_u else None,
+                                      _ptr(dn_bc) if want_d else None), "gdm_eval_trace")
+        if want_u and want_d:
+            return u_bc, dn_bc
+        return u_bc if want_u else dn_bc
+
+    def eval_grid_tile(self):
+        """(cells_x, cells_y, cells_z) of one work item of the evaluation kernel, kernel axes"""
+        return _capi.eval_grid_tile(self.p, self.dim)
+
     # -- direct heat-implicit / Poisson solve (fast diagonalisation) -------------
     @property
     def nitsche(self):

@@ -242,6 +242,100 @@ class HeatProblem(WaveProblem):
             stage = Y
 
 
+class QuasilinearHeatProblem:
+    """Quasi-linear heat conduction u_t = M^-1 (K[kappa(u)] u + data(t)) on one
+    rank and an uncut box by classic RK4: K[kappa] the wave operator of `op`
+    (kind "wave") with the coefficient on the Gauss grid
+    (GdmOperator.set_coefficient_grid), kappa re-evaluated from the stage
+    vector before every stage's apply.
+
+    kappa: a callable on device tensors, elementwise, with values > 0 (for
+    instance lambda u: 1 + u * u).  The problem owns the grid arrays kq and kbc
+    that the engine borrows.  They are set once, from the initial u, by the
+    first step (the only set call, with its check that kappa > 0); after that
+    every stage refreshes them in place, kq.copy_(kappa(eval_grid(stage))) and,
+    with nitsche > 0, kbc.copy_(kappa(eval_trace(stage))): no set call, no
+    reduction and no host synchronisation per stage.  Positivity of kappa at
+    the later stages is therefore the caller's responsibility: a sample that
+    is not positive is not reported, the step is then not parabolic.
+
+    forcing / dirichlet as in WaveProblem (add_data); the Dirichlet data term
+    uses the refreshed kbc."""
+
+    def __init__(self, op, kappa, forcing=None, dirichlet=None):
+        import torch
+
+        from .operator import KINDS
+
+        if op.mesh.n_ranks != 1:
+            raise GdmError("QuasilinearHeatProblem: single-rank driver")
+        if op.kind != KINDS["wave"]:
+            raise GdmError("QuasilinearHeatProblem: a 'wave' operator is needed")
+        if not callable(kappa):
+            raise GdmError("QuasilinearHeatProblem: kappa is a callable on device tensors")
+        if dirichlet is not None and not op.nitsche > 0.0:
+            raise GdmError("QuasilinearHeatProblem: Dirichlet data needs an operator with nitsche > 0")
+        self.op, self.kappa = op, kappa
+        self.forcing, self.dirichlet = forcing, dirichlet
+        dev = "cuda:%d" % op.device
+        # the boundary values of a built-in g_D (add_data)
+        self._g = None
+        if dirichlet is not None and not callable(dirichlet):
+            self._g = torch.zeros(op.n_bc_points, dtype=torch.float64, device=dev)
+        self.u = op.new_vector(False)
+        self._acc, self._Y, self._k = (op.new_vector(False) for _ in range(3))
+        self.kq = torch.empty(op.n_grid_points, dtype=torch.float64, device=dev)
+        self._uq = torch.empty_like(self.kq)
+        self._face = op.nitsche > 0.0 and op.n_bc_points > 0
+        self.kbc = torch.empty(op.n_bc_points, dtype=torch.float64, device=dev) if self._face else None
+        self._ubc = torch.empty_like(self.kbc) if self._face else None
+        self._set = False
+        self.last_stage = None
+
+    def refresh(self, stage):
+        """kq (and kbc) = kappa of the stage vector at the Gauss points (the boundary points), in place"""
+        op = self.op
+        self.kq.copy_(self.kappa(op.eval_grid(stage, self._uq, False)))
+        if self._face:
+            self.kbc.copy_(self.kappa(op.eval_trace(stage, self._ubc, False)))
+
+    def rhs(self, t, stage, out):
+        """out = K[kappa(stage)] stage + data(t)"""
+        self.refresh(stage)
+        if not self._set:
+            self.op.set_coefficient_grid(self.kq, self.kbc)
+            self._set = True
+        self.op.apply(stage, out)
+        self.add_data(t, out)
+        return out
+
+    add_data = WaveProblem.add_data
+
+    def step(self, t, h):
+        op, u, k = self.op, self.u, self._k
+        acc, Y = self._acc, self._Y
+        stage = u
+        for s in range(4):
+            self.last_stage = stage  # kq / kbc hold kappa of this vector until the next refresh
+            self.rhs(t + RK4_C[s] * h, stage, k)
+            last = s == 3
+            op.mass_solve_rk(k, h * RK4_B[s], u if s == 0 else acc, u if last else acc,
+                             0.0 if last else h * RK4_A[s], None if last else u, None if last else Y)
+            stage = Y
+
+    def run(self, start_t, end_t, dt, max_steps=None, callback=None):
+        time = DiscreteTime(start_t, end_t, dt)
+        n = 0
+        while not time.is_at_end() and (max_steps is None or n < max_steps):
+            h = time.next_step_size()
+            self.step(time.t, h)
+            n += 1
+            if callback is not None:
+                callback(time.t + h, self)
+            time.advance()
+        return n
+
+
 def solve_poisson(op, forcing=None, dirichlet=None, t=0.0, rel_tol=1e-8, abs_tol=1e-30, max_it=1000, info=None):
     """The "poisson" simulation type (wave/problem.h:46-71) on an uncut box:
     the device solution of S u = data(t), S = -K of the wave operator `op`

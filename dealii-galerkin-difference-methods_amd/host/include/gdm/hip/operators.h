@@ -394,6 +394,33 @@ class StiffnessMatrixOperator {
           "gdm_add_boundary_fn");
   }
 
+  // Grid evaluation (single rank, non-periodic): what fe_values.get_function_values / get_function_gradients
+  // give the reference's cell loops, for every cell at once on the tensor Gauss grid (gdm_eval_grid; x fastest,
+  // gradients component-major).  n_grid_points() sizes the arrays; either output alone costs nothing for the other.
+  int64_t n_grid_points() const {
+    const gdm_mesh_desc &m = discretization.get_mesh();
+    int64_t n = 1;
+    for (int d = 0; d < dim; ++d) n *= (int64_t)m.n_subdivisions[d] * (m.fe_degree + 1);
+    return n;
+  }
+  void get_function_values(const DeviceVector &u, DeviceVector &values) const {
+    check(gdm_eval_grid(op, u.get_values(), values.get_values(), nullptr), "gdm_eval_grid");
+  }
+  void get_function_gradients(const DeviceVector &u, DeviceVector &gradients) const {
+    check(gdm_eval_grid(op, u.get_values(), nullptr, gradients.get_values()), "gdm_eval_grid");
+  }
+  void get_function_values_and_gradients(const DeviceVector &u, DeviceVector &values, DeviceVector &gradients) const {
+    check(gdm_eval_grid(op, u.get_values(), values.get_values(), gradients.get_values()), "gdm_eval_grid");
+  }
+  // dst (owned) += scale sum_e (d_e v, F_e): the cell loop's shape_grad(i, q) * F(q) * JxW(q) (gdm_add_load_grad)
+  void integrate_gradients(const DeviceVector &flux, DeviceVector &dst, double scale = 1.0) const {
+    check(gdm_add_load_grad(op, flux.get_values(), scale, owned(dst)), "gdm_add_load_grad");
+  }
+  // the wall trace and outward normal derivative at the boundary points, block(0) order (gdm_eval_trace)
+  void get_function_trace(const DeviceVector &u, DeviceVector &trace, DeviceVector &normal_derivative) const {
+    check(gdm_eval_trace(op, u.get_values(), trace.get_values(), normal_derivative.get_values()), "gdm_eval_trace");
+  }
+
   gdm_op *handle() const { return op; }
   const gdm_layout &get_layout() const { return layout; }
   double *owned(DeviceVector &v) const { return v.get_values() + layout.ghost_planes_below * layout.plane_size; }

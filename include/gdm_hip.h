@@ -851,6 +851,52 @@ int gdm_load_vector_1d(const gdm_mesh_desc *mesh, int axis, const double *f, dou
 int gdm_load_tile(int fe_degree, int dim, int *tile_x, int *tile_y, int *z_chunk);
 
 /* ------------------------------------------------------------------------
+ * Grid evaluation: u and grad u on the tensor Gauss grid, the flux load and
+ * the wall trace -- with gdm_add_load the three legs of a matrix-free
+ * "evaluate, pointwise work, integrate" cycle, so that a quasi-linear problem
+ * -div F(x, u, grad u) = f(x, u) is grid evaluation, pointwise work on the
+ * grid arrays and grid integration (gdm_amd.QuasilinearHeatProblem).
+ * Q_d = n_sub_d (p+1), Q = prod Q_d; grid arrays in gdm_add_load's fq layout
+ * (x fastest); vector-valued grid arrays component-major, gq[e Q + q] with e
+ * the reference direction.
+ *   gdm_eval_grid        uq[Q] = u and gq[dim Q] = the physical gradient of u
+ *                        at the Gauss points: FEValues::get_function_values
+ *                        and get_function_gradients of every cell at once
+ *                        (wave/stiffness.h:151-203, advection/problem.h:
+ *                        330-425).  Either output may be NULL (it then costs
+ *                        nothing); both NULL is GDM_ERR_ARG.  The outputs must
+ *                        not overlap u_local (GDM_ERR_ARG).  One launch.
+ *   gdm_add_load_grad    dst += scale sum_e (d_e v, F_e) over QGauss(p+1),
+ *                        Fq[dim Q] as gq: the cell loop's
+ *                        fe_values.shape_grad(i, q) * F(q) * JxW(q)
+ *                        (wave/stiffness.h:171-181 with F in place of grad u),
+ *                        the transpose of the gradient evaluation with the
+ *                        Gauss weights.  One launch, dst is read and written
+ *                        once; scale == 0 launches nothing.
+ *   gdm_eval_trace       u_bc / dn_bc [n_bc_points] = the wall trace and the
+ *                        outward normal derivative of u at the boundary points
+ *                        in the device block(0) order (gdm_bc_points, g_bc,
+ *                        kbc): FEFaceValues::get_function_values and
+ *                        get_function_gradients . normal_vector of the box
+ *                        faces (wave/stiffness.h:296-310).  Either output may
+ *                        be NULL, not both; a no-op with n_bc_points == 0.
+ *   gdm_eval_grid_tile   pure host: the block of cells that one work item of
+ *                        the evaluation kernel owns, kernel axes (3D: x, y, z;
+ *                        2D: x, y, -; 1D: -, -, x)
+ * Every operator kind; on an elasticity operator a call takes one component
+ * (pass the component's block of the component-major vector).
+ * GDM_ERR_UNSUPPORTED: n_ranks > 1, a periodic mesh, the inner operator of a
+ * cut handle.  All tables are built by gdm_op_create; no call allocates or
+ * synchronises, so a first call may be captured in a hipGraph.  Every output
+ * value is formed by one thread in a fixed order and stored once: the bits do
+ * not depend on the launch, the stream or a graph replay.
+ * ---------------------------------------------------------------------- */
+int gdm_eval_grid(gdm_op *op, const double *u_local, double *uq, double *gq);
+int gdm_add_load_grad(gdm_op *op, const double *Fq, double scale, double *dst_owned);
+int gdm_eval_trace(gdm_op *op, const double *u_local, double *u_bc, double *dn_bc);
+int gdm_eval_grid_tile(int fe_degree, int dim, int *cx, int *cy, int *cz);
+
+/* ------------------------------------------------------------------------
  * Direct solve with the uncut wave / heat operator by fast diagonalisation
  * (added within ABI 18: new entry points only, backward compatible, the
  * version number is unchanged).  The linear solves of the "poisson" and
